@@ -26,16 +26,24 @@ produces), so it overlaps the next env step the way it would overlap a backward 
 --serial-collective puts it on the step's stream instead.
 At N = 1 the step is the env step alone (the headline).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: the contract
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step),
+`config` and, at N > 1, `collective.ranks_seen`.
+--dump-outputs DIR writes what the last timed step returned (obs, vo_count, reward, done, info, finish) as
+float32 DIR/<name>.npy, on a fixed seeded sample of the envs when the whole batch exceeds the size cap.
+--full adds every measurement that takes runs of its own:
   roofline     : algorithmic bytes per launch / average kernel time (HIP events on
                  the launch stream) against the 8 TB/s HBM peak; `traffic` (HBM bytes per
                  launch) and `fp64_valu_tflops` come from the PMC record of this very
                  command (profiles/traffic.json, written by tools/pmc_record.sh: separate
-                 rocprofv3 --pmc passes) - `traffic_source` says so
+                 rocprofv3 --pmc passes) - `traffic_source` says so; kernel_ms_cold / frac_cold
+                 (cache-cold launches)
+  rollout      : BASELINE config 3 as written (policy forward -> env step -> buffer stores,
+                 GAE, PPO update), in a child process
   cpu_baseline : the CPU oracle (oracle/, the validated C restatement of the
                  reference step) timed on this host on a bounded sample, on 1 thread
                  and on every core the process may use
-  collective   : (N > 1) ranks_seen, allreduce_us, bucket bytes.
+  collective   : (N > 1) allreduce_us, bucket bytes, the same K steps without the collective.
 """
 from __future__ import annotations
 
@@ -53,6 +61,8 @@ import torch
 
 ALLOW_DIAG = False  # set by tools/bench_diag.py only (the -DRVO3D_DIAG build of the library)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.29 TB/s measured copy)
+DUMP_BYTES = 60_000_000  # --dump-outputs writes at most this many bytes of arrays (64 MB with headroom)
+DUMP_NAMES = ("obs", "vo_count", "reward", "done", "info", "finish")  # what env.step returns, in order
 
 
 def algorithmic_bytes_per_drone_step(nm: int, nb: int, N: int) -> float:
@@ -118,6 +128,22 @@ def cpu_baseline(N, nm, map_size, seconds_target=12.0):
                       f"(affinity {affinity}, cgroup quota {quota})"}
 
 
+def dump_outputs(path, outs, seed=1234):
+    """--dump-outputs: the arrays env.step returned in the last timed step, as float32 <path>/<name>.npy (vo_count and
+    the flags are exact in float32).  When the whole batch exceeds DUMP_BYTES, the same fixed, seeded sample of envs
+    (sorted env indices) is written for every array.  Returns what was written, for the result line."""
+    host = {n: t.detach().cpu().numpy() for n, t in zip(DUMP_NAMES, outs)}
+    E = host["obs"].shape[0]
+    per_env = sum(a[0].size for a in host.values()) * 4
+    keep = min(E, max(1, DUMP_BYTES // per_env))
+    idx = np.arange(E) if keep == E else np.sort(np.random.default_rng(seed).choice(E, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for n, a in host.items():
+        np.save(os.path.join(path, n + ".npy"), np.ascontiguousarray(a[idx], dtype=np.float32))
+    return {"files": [n + ".npy" for n in DUMP_NAMES], "dtype": "float32", "envs": int(keep), "of_envs": int(E),
+            "sample": "all envs" if keep == E else f"np.random.default_rng({seed}).choice({E}, {keep}, replace=False), sorted"}
+
+
 class GradBucket:
     """The policy-gradient collective of one optimizer step, through the trainer's own code
     (multi_ppo._allreduce_grads + the KL mean of multi_ppo.update): MLP(256,256) actor-critic of
@@ -165,6 +191,12 @@ def parse_args(argv=None):
     ap.add_argument("--nm", type=int, default=10)
     ap.add_argument("--buildings", type=int, default=0)
     ap.add_argument("--map", type=float, nargs=3, default=[50.0, 50.0, 10.0])
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: roofline (warm and cache-cold kernel time), the "
+                         "rollout block, cpu_baseline and, at N > 1, the collective's own timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as float32 DIR/<name>.npy (at most 64 MB: a "
+                         "fixed, seeded sample of the envs when the batch is larger)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-autoreset", action="store_true")
     ap.add_argument("--grad-allreduce", action="store_true",
@@ -422,13 +454,14 @@ def run_rank(args):
     def one_step(t):
         if flush is not None:
             flush()
-        env.step(acts[t % n_act], autoreset=autoreset)
+        outs = env.step(acts[t % n_act], autoreset=autoreset)
         if bucket is not None and t % every == 0:
             if side is not None:
                 with torch.cuda.stream(side):
                     bucket.step()
             else:
                 bucket.step()
+        return outs
 
     def barrier():
         if dist is not None:
@@ -440,13 +473,18 @@ def run_rank(args):
     for t in range(W):
         one_step(t)
     barrier()
+    outs = None
     t0 = time.perf_counter()
     for t in range(K):
-        one_step(W + t)
+        outs = one_step(W + t)
     barrier()
     elapsed = sharding.max_over_ranks(dist, time.perf_counter() - t0, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0 and outs is not None:
+        # env.step returns views of the handle's own buffers: written before any further step
+        dumped = dump_outputs(args.dump_outputs, outs)
     elapsed_step_only = None
-    if bucket is not None:  # the same K steps without the collective, for comparison (not `value`)
+    if bucket is not None and args.full:  # the same K steps without the collective, for comparison (not `value`)
         barrier()
         t1 = time.perf_counter()
         for t in range(K):
@@ -479,12 +517,13 @@ def run_rank(args):
         ok = ts <= 3.0 * med
         return float(ts[ok].mean()), med, float(ts.mean()), int((~ok).sum())
 
-    kern_ms, kern_med_ms, kern_mean_all_ms, kern_dropped = timed_launches(flush)
+    kern_ms = kern_cold_ms = None
+    if args.full:
+        kern_ms, kern_med_ms, kern_mean_all_ms, kern_dropped = timed_launches(flush)
     # cache-cold: back-to-back launches find the ~54 MB of state the previous launch wrote still in the
     # 256 MiB Infinity Cache; a trainer runs policy GEMMs over several hundred MB between two env steps.
     # Here a scratch buffer of --cold-mb MiB is read and rewritten between two timed launches.
-    kern_cold_ms = None
-    if not args.no_cold:
+    if args.full and not args.no_cold:
         scratch = torch.zeros(max(args.cold_mb, 1) << 20, dtype=torch.uint8, device=dev)
         kern_cold_ms = timed_launches((lambda: scratch.add_(1)) if args.cold_mode == "rw" else (lambda: scratch.sum()))[0]
         del scratch
@@ -495,48 +534,33 @@ def run_rank(args):
         ones = torch.ones(1, dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(ones)
         ranks_seen = int(round(float(ones.item())))
-    if bucket is not None:  # the collective alone, same stream, K repetitions
-        ce = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
-        for a, b in ce:
-            a.record(stream)
-            bucket.step()
-            b.record(stream)
-        torch.cuda.synchronize()
+    if bucket is not None:
         coll = dict(ranks_seen=ranks_seen,
                     backend=("nccl (RCCL)" if args.backend == "nccl" else args.backend) if dist is not None else "none (1 rank)",
-                    allreduce_us=round(float(np.mean([a.elapsed_time(b) for a, b in ce])) * 1e3, 2),
                     overlapped=side is not None,
                     bucket_bytes=bucket.nbytes, env_steps_per_allreduce=every,
                     per_step="ONE all-reduce of the gradient bucket with the KL estimate in its last slot "
                     f"(multi_ppo._allreduce_grads) per {every} timed env step(s)")
+        if args.full:  # the collective alone, same stream, K repetitions
+            ce = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
+            for a, b in ce:
+                a.record(stream)
+                bucket.step()
+                b.record(stream)
+            torch.cuda.synchronize()
+            coll["allreduce_us"] = round(float(np.mean([a.elapsed_time(b) for a, b in ce])) * 1e3, 2)
     elif world > 1:
         coll = dict(ranks_seen=ranks_seen, backend="nccl (RCCL)" if args.backend == "nccl" else args.backend,
                     per_step="none (--no-grad-allreduce)")
 
     rollout = None
-    if not args.no_rollout and rank == 0 and world == 1:
+    if args.full and not args.no_rollout and rank == 0 and world == 1:
         rollout = rollout_in_child(args) if not args.rollout_inline else rollout_block(env, args)
 
     status = 0
     if rank == 0:
         total_units = world * E * N * K
         value = total_units / elapsed
-        B = algorithmic_bytes_per_drone_step(nm, nb, N)
-        bytes_per_launch = E * N * B
-        achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
-        traffic = fp64_flops = None
-        traffic_source = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        key = f"{N}x{E}" + (f"+{nb}b" if nb else "")
-        if os.path.exists(tpath):
-            try:
-                rec = json.load(open(tpath)).get(key)
-                if isinstance(rec, dict):
-                    traffic, fp64_flops = rec.get("hbm_bytes"), rec.get("fp64_flops")
-                    traffic_source = ("profiles/traffic.json[%s]: builder's rocprofv3 --pmc passes of this "
-                                      "command (%s), not measured in this run" % (key, rec.get("source", "tools/pmc_record.sh")))
-            except Exception:
-                traffic = None
         out = {
             "metric": "drone-steps/sec (env.step throughput)",
             "value": round(value, 1), "unit": "drone-steps/s", "n_gpus": ranks_seen, "steps": K,
@@ -550,39 +574,23 @@ def run_rank(args):
                        "cold_all": bool(args.cold_all),
                        "ablate": int(os.environ.get("RVO3D_ABLATE", "0")) if diag else 0,
                        "device_error_word": flags},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "fp64_valu_tflops": (round(fp64_flops / (kern_ms * 1e-3) / 1e12, 3)
-                                              if fp64_flops else None),
-                         "fp64_valu_peak_tflops": 78.6,
-                         # the instantiation the library launches for this handle (rvo3d_kernel_name)
-                         "kernel": env.kernel_name("step_autoreset" if autoreset else "step"),
-                         "kernel_ms": round(kern_ms, 4),  # mean over the K event pairs without host-stall samples
-                         "kernel_ms_median": round(kern_med_ms, 4), "kernel_ms_mean_all_samples": round(kern_mean_all_ms, 4),
-                         "host_stall_samples_dropped": kern_dropped,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "bytes_per_drone_step": B},
         }
-        if kern_cold_ms is not None:
-            ach_cold = bytes_per_launch / (kern_cold_ms * 1e-3) / 1e9
-            out["roofline"].update({
-                "kernel_ms_cold": round(kern_cold_ms, 4), "achieved_cold": round(ach_cold, 2),
-                "frac_cold": round(ach_cold / HBM_PEAK_GBS, 5),
-                "cold": f"{args.cold_mb} MiB of scratch {'read and rewritten' if args.cold_mode == 'rw' else 'read'} on the launch stream between two "
-                        "timed launches (outside the event pairs): nothing of the previous step is left in "
-                        "the 256 MiB Infinity Cache - the regime of a rollout with policy GEMMs between env steps"})
+        if kern_ms is not None:
+            out["roofline"] = roofline_record(env, args, kern_ms, kern_med_ms, kern_mean_all_ms, kern_dropped, kern_cold_ms)
         if coll is not None:
+            if bucket is not None:
+                out["config"]["workload"] += (f"; + gradient-bucket all-reduce and KL mean every {every} step(s)" +
+                                              (" on a second stream" if side is not None else ""))
             if elapsed_step_only is not None:
                 coll["value_env_step_only"] = round(total_units / elapsed_step_only, 1)
                 coll["ms_per_step_env_step_only"] = round(elapsed_step_only / K * 1e3, 4)
-                out["config"]["workload"] += (f"; + gradient-bucket all-reduce and KL mean every {every} step(s)" +
-                                              (" on a second stream" if side is not None else ""))
             out["collective"] = coll
         if rollout is not None:
             out["rollout"] = rollout
-        if not args.no_cpu_baseline and world == 1:  # reported once, at N = 1
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported once, at N = 1
             out["cpu_baseline"] = cpu_baseline(N, nm, tuple(args.map))
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if ranks_seen != args.gpus:
             out["error"] = f"--gpus {args.gpus} but the all-reduce saw {ranks_seen} rank(s)"
             status = 3
@@ -592,6 +600,51 @@ def run_rank(args):
         dist.barrier()
         dist.destroy_process_group()
     return status
+
+
+def roofline_record(env, args, kern_ms, kern_med_ms, kern_mean_all_ms, kern_dropped, kern_cold_ms):
+    """--full: the fused step's kernel time (HIP event pairs) against the HBM roofline, warm and cache-cold, with the
+    PMC record of this command from profiles/traffic.json when there is one."""
+    E, N, nm, nb = args.envs, args.drones, args.nm, args.buildings
+    autoreset = not args.no_autoreset
+    B = algorithmic_bytes_per_drone_step(nm, nb, N)
+    bytes_per_launch = E * N * B
+    achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
+    traffic = fp64_flops = None
+    traffic_source = None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    key = f"{N}x{E}" + (f"+{nb}b" if nb else "")
+    if os.path.exists(tpath):
+        try:
+            rec = json.load(open(tpath)).get(key)
+            if isinstance(rec, dict):
+                traffic, fp64_flops = rec.get("hbm_bytes"), rec.get("fp64_flops")
+                traffic_source = ("profiles/traffic.json[%s]: builder's rocprofv3 --pmc passes of this "
+                                  "command (%s), not measured in this run" % (key, rec.get("source", "tools/pmc_record.sh")))
+        except Exception:
+            traffic = None
+    roof = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+            "traffic": traffic, "traffic_source": traffic_source,
+            "fp64_valu_tflops": (round(fp64_flops / (kern_ms * 1e-3) / 1e12, 3)
+                                 if fp64_flops else None),
+            "fp64_valu_peak_tflops": 78.6,
+            # the instantiation the library launches for this handle (rvo3d_kernel_name)
+            "kernel": env.kernel_name("step_autoreset" if autoreset else "step"),
+            "kernel_ms": round(kern_ms, 4),  # mean over the K event pairs without host-stall samples
+            "kernel_ms_median": round(kern_med_ms, 4), "kernel_ms_mean_all_samples": round(kern_mean_all_ms, 4),
+            "host_stall_samples_dropped": kern_dropped,
+            "algorithmic_bytes_per_launch": bytes_per_launch,
+            "bytes_per_drone_step": B}
+    if kern_cold_ms is not None:
+        ach_cold = bytes_per_launch / (kern_cold_ms * 1e-3) / 1e9
+        roof.update({
+            "kernel_ms_cold": round(kern_cold_ms, 4), "achieved_cold": round(ach_cold, 2),
+            "frac_cold": round(ach_cold / HBM_PEAK_GBS, 5),
+            "cold": f"{args.cold_mb} MiB of scratch {'read and rewritten' if args.cold_mode == 'rw' else 'read'} on the launch stream between two "
+                    "timed launches (outside the event pairs): nothing of the previous step is left in "
+                    "the 256 MiB Infinity Cache - the regime of a rollout with policy GEMMs between env steps"})
+    return roof
 
 
 def policy_kernel_roofline(tr, env):

@@ -4,7 +4,7 @@ TAG=${1:-run}
 OUT=gpurun_out/bench_all_$TAG.txt
 : > $OUT
 run() {
-  python bench.py --no-cpu-baseline --no-rollout --steps 200 "$@" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-rollout --steps 200 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

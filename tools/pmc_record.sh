@@ -13,7 +13,7 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/pmc_record_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $ROOT/bench.py --no-cpu-baseline $*"
+CMD="python3 $ROOT/bench.py --full --no-cpu-baseline $*"
 echo "command: rocprofv3 ... -- $CMD" > $OUT/command.txt
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1 || echo "trace pass failed" >> $OUT/fail.log
 i=0

@@ -25,7 +25,7 @@ done
 for k in cold rollout rollout_rnn; do f=$(find $OUT/${k}_trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -16 $f > $OUT/${k}_kernel_stats.csv; done
 rm -rf $OUT/cold_trace $OUT/rollout_trace $OUT/rollout_rnn_trace
 bash tools/bench_all.sh $R > /dev/null 2>&1; cp gpurun_out/bench_all_$R.txt $OUT/bench_all_shapes.txt
-python bench.py > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+python bench.py --full > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
 python tools/bench_rollout.py --amp --steps 16 > $OUT/rollout_bench.json 2>/dev/null
 python tools/rollout_profile.py > $OUT/rollout_step_kernels.txt 2>/dev/null
 python tools/rollout_profile.py --policy rnn > $OUT/rollout_step_kernels_rnn.txt 2>/dev/null
