@@ -573,7 +573,8 @@ int rvo3d_observe(rvo3d_env* h, float* obs, int32_t* vo_count, void* stream) {
 
 static int step_common(rvo3d_env* h, const void* actions, int32_t action_dtype, float* obs,
                        int32_t* vo_count, float* reward, uint8_t* done, uint8_t* info,
-                       uint8_t* finish, uint8_t* reset_mask, bool autoreset, void* stream) {
+                       uint8_t* finish, uint8_t* reset_mask, bool autoreset, void* stream,
+                       const int32_t* prev_cnt = nullptr) {
   RVO3D_API_BEGIN
   DeviceGuard dg;
   int rc = check(h, true, dg);
@@ -587,6 +588,7 @@ static int step_common(rvo3d_env* h, const void* actions, int32_t action_dtype, 
   P.obs = obs; P.vo_count = vo_count; P.reward = reward;
   P.zf16 = (h->cold.zf_q != 0 && (reinterpret_cast<uintptr_t>(obs) & 15) == 0 && P.nm > 0) ? 1 : 0;
   P.done = done; P.info = info; P.finish = finish; P.reset_mask = reset_mask;
+  P.prev_cnt = prev_cnt;  // (h->P's is always null: nothing of it outlives the call)
   P.dv_cached = h->dv_valid ? 1 : 0;
   P.g_cached = h->g_valid ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -607,13 +609,14 @@ int rvo3d_step(rvo3d_env* h, const void* actions, int32_t action_dtype, float* o
 
 static int step_policy_common(rvo3d_env* h, const float* a_inc, float acceler, float* obs,
                               int32_t* vo_count, float* reward, uint8_t* done, uint8_t* info,
-                              uint8_t* finish, uint8_t* reset_mask, bool autoreset, void* stream) {
+                              uint8_t* finish, uint8_t* reset_mask, bool autoreset, void* stream,
+                              const int32_t* prev_cnt = nullptr) {
   RVO3D_API_BEGIN
   if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
   h->P.action_mode = 1;
   h->P.acceler = acceler;
   const int rc = step_common(h, a_inc, RVO3D_F32, obs, vo_count, reward, done, info, finish,
-                             reset_mask, autoreset, stream);
+                             reset_mask, autoreset, stream, prev_cnt);
   h->P.action_mode = 0;
   return rc;
   RVO3D_API_END
@@ -634,6 +637,18 @@ int rvo3d_step_autoreset(rvo3d_env* h, const void* actions, int32_t action_dtype
   RVO3D_API_BEGIN
   return step_common(h, actions, action_dtype, obs, vo_count, reward, done, info, finish,
                      reset_mask, true, stream);
+  RVO3D_API_END
+}
+
+int rvo3d_step_ex(rvo3d_env* h, const rvo3d_step_args* a, void* stream) {
+  RVO3D_API_BEGIN
+  if (!a) return fail(RVO3D_ERR_INVALID, "null argument");
+  if (a->policy)
+    return step_policy_common(h, static_cast<const float*>(a->actions), a->acceler, a->obs, a->vo_count, a->reward,
+                              a->done, a->info, a->finish, a->reset_mask, a->autoreset != 0, stream,
+                              a->prev_vo_count);
+  return step_common(h, a->actions, a->action_dtype, a->obs, a->vo_count, a->reward, a->done, a->info, a->finish,
+                     a->autoreset ? a->reset_mask : nullptr, a->autoreset != 0, stream, a->prev_vo_count);
   RVO3D_API_END
 }
 

@@ -10,9 +10,10 @@ namespace rvo3d {
 // ---- LDS views ---------------------------------------------------------------
 struct Lds {
   double *x, *y, *z, *vx, *vy, *vz, *r, *prio;  // [T] fp64 image (exact stage)
-  int* kept;                                     // [T] rows kept by the final sweep
+  int* kept;                                     // [T] rows kept by the final sweep (before: the old counts, prev_cnt)
   int* any_reset;                                // [epb]
   int* far;                                      // [epb] a drone is outside the fp32 filter's bound
+  int* any_old;                                  // [1] some row of the workgroup had old kept rows (prev_cnt)
   // fp32 image, each env's N slots stored twice ([el][2N]) so that neighbour
   // d + k (mod N) is slot d + k; and the exact-stage request masks
   float* w[12];                                  // x y z r [FL] (stored twice); vx vy vz kd ax ay az prio [FS]
@@ -51,6 +52,7 @@ __device__ __forceinline__ Lds carve_lds(unsigned char* base, int T, int nm, int
   L.w[9] = ws + 5 * FS; L.w[10] = ws + 6 * FS; L.w[11] = ws + 7 * FS;
   L.any_reset = reinterpret_cast<int*>(ws + 8 * (size_t)FS);
   L.far = L.any_reset + epb;
+  L.any_old = L.far + epb;
   L.T = T;
   return L;
 }
@@ -58,7 +60,7 @@ __host__ __device__ inline size_t lds_bytes(int T, int nm, int epb, int N, int N
   (void)nm;
   return (size_t)T * 8 * 8 + (size_t)T * NW * 8 + (size_t)T * 4 +
          (size_t)f32_len_nw(T, N, epb, NW) * 16 + (size_t)f32_single_nw(N, epb, NW) * 32 +
-         (size_t)epb * 8 + 16;
+         (size_t)epb * 8 + 4 + 16;
 }
 
 __device__ __forceinline__ Drone lds_drone(const Lds& L, int k) {

@@ -147,6 +147,11 @@ struct Params {
   float* reward;
   double* reward64;   // optional: the same reward as the reference returns it, float64 (mdin.py:28)
   uint8_t *done, *info, *finish, *reset_mask;
+  // optional: obs / vo_count hold a consistent pair (both last written by one call of this library) whose
+  // counts are these - every float of row r past 12 + 9 * prev_cnt[r] is already zero.  May alias vo_count:
+  // a drone reads its old count in phase 0, long before it stores the new one (no __restrict__ anywhere
+  // lets the compiler move the two past each other).
+  const int32_t* prev_cnt;
 };
 
 // Diagnostics exist only in the -DRVO3D_DIAG build (librvo3d_hip_diag.so, made and loaded by

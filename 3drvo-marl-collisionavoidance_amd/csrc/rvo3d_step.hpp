@@ -205,6 +205,9 @@ __device__ __forceinline__ bool two_phase_rows(const Params& P, int row0, int nr
 
 // part 1: zeros of every 64-B block that holds no proprio byte.  One wave-instruction = 16 blocks
 // (1 KB, whole lines).
+// With P.prev_cnt (obs holds a consistent pair) a block is stored only where it overlaps an old kept-row
+// range [48, 48 + 36 * cnt_old) of its row: every other byte of it is zero already, and the kept rows of
+// this step go over it as before.  L.kept holds the old counts (phase 0) until the rows are staged.
 template <int NW>
 __device__ __forceinline__ void early_zero_blocks(const Params& P, const Lds& L, int tid, int row0,
                                                   int nrows) {
@@ -220,6 +223,27 @@ __device__ __forceinline__ void early_zero_blocks(const Params& P, const Lds& L,
   // windows of part 2, whose lines are shared with the kept rows, are faster as ordinary stores)
   const int iters = P.cold().zf_iters;
   uint32_t m = P.cold().zmask[tid >> 2];
+  if (P.prev_cnt) {
+    // the common case - no row of the workgroup had a kept row - stores nothing at all (L.kept: the
+    // workgroup's rows are [0, T) for one wave; several waves raised L.any_old in phase 0)
+    const bool any = NW == 1 ? __ballot(L.kept[tid] != 0) != 0
+                             : __builtin_amdgcn_readfirstlane(*L.any_old) != 0;
+    if (!any) return;
+    // trip i meets the block at byte o = blk * 64 + i * 1024 * nwv of the workgroup's rows, inside the VO
+    // region of row o / rb.  With zf_iters <= 32 and >= 8 rows, o < 2^18 (exact in fp32) and rb <= 2^15: the
+    // quotient (< 512) is >= 48 / rb >= 2^-10 away from an integer (an early block starts >= 48 B into a row
+    // and ends inside it), the fp32 product is off by < 2^-14 and truncates to the row exactly.
+    const float inv_rb = 1.0f / (float)rb;
+    const uint32_t st = 1024u * (uint32_t)nwv;
+    uint32_t keep = 0;
+    for (int i = 0; i < iters; ++i)
+      if ((m >> i) & 1u) {
+        const uint32_t o = blk * 64u + (uint32_t)i * st;
+        const uint32_t r = (uint32_t)((float)o * inv_rb);
+        if (o - r * rb < 48u + 36u * (uint32_t)L.kept[r]) keep |= 1u << i;
+      }
+    m = keep;
+  }
   char* p = base + (size_t)blk * 64u + 16u * ((uint32_t)ln & 3u);
   const size_t step = (size_t)1024 * (size_t)nwv;
   // four trips per loop pass (bits beyond the last trip are 0: nothing is stored for them)
@@ -429,9 +453,6 @@ enum Mode { kObserve = 0, kStep = 1, kStepAutoReset = 2 };
 #ifndef RVO3D_ZERO_NT
 #define RVO3D_ZERO_NT 1  // streaming (non-temporal) stores for the early zero blocks
 #endif
-#ifndef RVO3D_STAGGER_ZEROS
-#define RVO3D_STAGGER_ZEROS 0
-#endif
 #ifndef RVO3D_DEPHASE
 #define RVO3D_DEPHASE 0
 #endif
@@ -487,27 +508,6 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   // stored as soon as they are final, so that across the sweeps little more than the
   // drone's own 8-value record and its action stay live (registers = waves per SIMD).
   RVO3D_STAMP(0);
-#if RVO3D_STAGGER_ZEROS
-  // (experiment, off: measured slower at 64 x 4096 both cache-warm, 40.1 -> 44.6 us, and cache-cold, 60.9 -> 63.3 us)
-  // Half of the workgroups store their early zero blocks (two-phase row writer: 69 % of the observation
-  // bytes, no data needed) at the very START, the other half where the reset decision is taken.  When a
-  // launch finds nothing in the caches (a rollout: policy GEMMs ran since the last step) all waves of the
-  // one resident round move through the phases together - everybody loads, everybody computes, everybody
-  // stores - and the memory system idles while they compute; with the two halves out of step the stores
-  // of one half fill the load / compute phases of the other.
-#if RVO3D_STAGGER_ZEROS == 2
-  // by the wave's slot on its SIMD (HW_ID bits 3:0), so that the waves sharing one SIMD are out of step
-  unsigned hw_id;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-  const bool odd_half = NW == 1 ? (hw_id & 1) : ((blockIdx.x >> 3) & 1);
-#else
-  const bool odd_half = (blockIdx.x >> 3) & 1;
-#endif
-  const bool zeros_first = LITE && odd_half && two_phase_rows(P, row0, nrows, full_rows);
-  if (zeros_first) early_zero_blocks<NW>(P, L, tid, row0, nrows);
-#else
-  const bool zeros_first = false;
-#endif
 #if RVO3D_DEPHASE
   // (experiment, off) waves in odd slots of their SIMD start RVO3D_DEPHASE x ~0.94 us (2048 cycles) late
   if (NW == 1) {
@@ -542,7 +542,16 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   //      state (waypoints, des_vel, deviation) is fetched after sweep A, which needs none of it
   uint32_t gw[NW];  // candidate words (stage G): on file from the previous step if it ended in this state
   const bool have_gw = MODE != kObserve && P.g_cached != 0;
+  // the old count of this drone's row (consistent obs / vo_count pair, early_zero_blocks), clamped to nm (a
+  // larger count only makes more blocks store); read before anything of this step is stored.  One-wave
+  // workgroups read it here; several waves where the reset state is requested (one register less across the
+  // sweeps: no spills there)
+  uint32_t old_cnt = 0;
   if (active) {
+    if (LITE && NW == 1 && P.prev_cnt) {
+      old_cnt = (uint32_t)P.prev_cnt[g];
+      old_cnt = old_cnt < (uint32_t)P.nm ? old_cnt : (uint32_t)P.nm;
+    }
     S.x = P.px()[g]; S.y = P.py()[g]; S.z = P.pz()[g];
     S.vx = P.vx()[g]; S.vy = P.vy()[g]; S.vz = P.vz()[g];
     if (P.uniform_rp) { S.r = P.r0; S.prio = P.prio0; }
@@ -586,8 +595,10 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   const double zero3[3] = {0, 0, 0};
 
   if (tid < P.epb) { L.any_reset[tid] = 0; L.far[tid] = 0; }
+  if (LITE && NW > 1 && tid == 0) *L.any_old = 0;
   L.kept[tid] = 0;
   __syncthreads();  // flags zeroed before anyone raises them
+  if (LITE && NW == 1 && active && P.prev_cnt) L.kept[lrow] = (int)old_cnt;  // until the rows are staged
   L.x[tid] = S.x; L.y[tid] = S.y; L.z[tid] = S.z;
   L.vx[tid] = S.vx; L.vy[tid] = S.vy; L.vz[tid] = S.vz;
   L.r[tid] = S.r; L.prio[tid] = S.prio;
@@ -802,6 +813,12 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     // few thousand cycles of store issue and needs no data at all: the loads land meanwhile
     double p[3] = {0, 0, 0}, rcur[3] = {0, 0, 0}, rdev = 0.0;
     uint32_t rdv_a = 0, rdv_b = 0;
+    if (NW > 1 && active && P.prev_cnt) {  // (see phase 0; visible to early_zero_blocks behind the next barrier)
+      old_cnt = (uint32_t)P.prev_cnt[g];
+      old_cnt = old_cnt < (uint32_t)P.nm ? old_cnt : (uint32_t)P.nm;
+      L.kept[lrow] = (int)old_cnt;
+      if (old_cnt != 0) *L.any_old = 1;
+    }
     if (do_reset) {  // (dronestate of the start state: static, tabulated by rvo3d_load_world, dv0_kernel)
       load_wp(P, g, 0, p);
       rdev = P.dev0()[g];
@@ -811,7 +828,7 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     RVO3D_STAMP(26);
     // (one-wave workgroups: 64 x 4096 -2 %; with several waves per workgroup the blocks go out right
     // before the rows sweep instead, which measured better there)
-    if (NW == 1 && !zeros_first && two_phase_rows(P, row0, nrows, full_rows) && !RVO3D_ABLATED(16)) early_zero_blocks<NW>(P, L, tid, row0, nrows);
+    if (NW == 1 && two_phase_rows(P, row0, nrows, full_rows) && !RVO3D_ABLATED(16)) early_zero_blocks<NW>(P, L, tid, row0, nrows);
     RVO3D_STAMP(27);
     if (do_reset) {  // drone.reset (drone.py:270-291); extra_len survives
       S.x = p[0]; S.y = p[1]; S.z = p[2]; S.vx = S.vy = S.vz = 0.0;
@@ -877,7 +894,7 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
       have_gw2 = true;
     }
     if (RVO3D_ABLATED(2)) have_gw2 = false;  // diagnostics: the collision sweep was skipped
-    if (NW > 1 && !zeros_first && two_phase_rows(P, row0, nrows, full_rows) && !RVO3D_ABLATED(16)) early_zero_blocks<NW>(P, L, tid, row0, nrows);
+    if (NW > 1 && two_phase_rows(P, row0, nrows, full_rows) && !RVO3D_ABLATED(16)) early_zero_blocks<NW>(P, L, tid, row0, nrows);
     kept = sweep_env<NW, true, false, TRAIN, GSH>(P, L, tid, el, d, g, active && !RVO3D_ABLATED(4), S, aa,
                                       false, flag, tmin, c2, gw, have_gw2);
   }

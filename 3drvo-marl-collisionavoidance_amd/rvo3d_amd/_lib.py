@@ -92,6 +92,14 @@ class RnnPolicy(C.Structure):
 RVO3D_F32, RVO3D_F64, RVO3D_BF16 = 0, 1, 2
 
 
+class StepArgs(C.Structure):
+    """rvo3d_step_args (rvo3d_step_ex)."""
+    _fields_ = [("actions", C.c_void_p), ("action_dtype", C.c_int32), ("policy", C.c_int32), ("acceler", C.c_float),
+                ("autoreset", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("obs", "vo_count", "reward", "done", "info", "finish", "reset_mask",
+                                          "prev_vo_count")]
+
+
 class StateView(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("px", "py", "pz", "vx", "vy", "vz", "yaw", "pitch", "real_len", "max_dev",
@@ -101,7 +109,7 @@ class StateView(C.Structure):
 # every symbol include/rvo3d.h declares (tests check the library exports them all)
 SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_reset",
            "rvo3d_reset_drones", "rvo3d_observe", "rvo3d_step", "rvo3d_step_autoreset",
-           "rvo3d_step_policy", "rvo3d_policy_sample", "rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_pack",
+           "rvo3d_step_policy", "rvo3d_step_ex", "rvo3d_policy_sample", "rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_pack",
            "rvo3d_policy_mlp_sample", "rvo3d_reader_zero_features", "rvo3d_policy_rows", "rvo3d_reader_first_step", "rvo3d_rollout_account", "rvo3d_rollout_set_step_counter", "rvo3d_set_reward_f64",
            "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
@@ -129,6 +137,7 @@ def lib():
     L.rvo3d_step.argtypes = [vp, vp, i32] + [vp] * 7
     L.rvo3d_step_autoreset.argtypes = [vp, vp, i32] + [vp] * 8
     L.rvo3d_step_policy.argtypes = [vp, vp, C.c_float] + [vp] * 7 + [i32, vp]
+    L.rvo3d_step_ex.argtypes = [vp, C.POINTER(StepArgs), vp]
     L.rvo3d_set_reward_f64.argtypes = [vp, vp]
     L.rvo3d_policy_sample.argtypes = [C.POINTER(PolicyHeads), C.c_int64, C.c_float, C.c_uint64, C.c_uint64] + [vp] * 6
     L.rvo3d_policy_mlp_blob_bytes.argtypes = [i32]

@@ -30,7 +30,10 @@ def _ptr(t):
 class BatchedDroneEnv:
     def __init__(self, world: World, neighbors_num: int = 10, env_train: bool = True,
                  device="cuda:0", action_decimals: int = -1, radius=None, priority=None,
-                 acceler: float = 0.5, reward_f64: bool = False):
+                 acceler: float = 0.5, reward_f64: bool = False, reuse_obs: bool = True):
+        """reuse_obs: a step into the env's own obs / vo_count leaves out the stores of the zeros the buffer
+        already holds, as long as the pair is what the library last wrote there (see `step`); False makes
+        every step write every byte."""
         if not torch.cuda.is_available():
             raise RuntimeError("rvo3d_amd needs a GPU: there is no CPU fallback "
                                "(the CPU oracle under oracle/ is test infrastructure only)")
@@ -69,6 +72,13 @@ class BatchedDroneEnv:
         self.info = torch.zeros((E, N), dtype=torch.uint8, device=dev)
         self.finish = torch.zeros((E, N), dtype=torch.uint8, device=dev)
         self.reset_mask = torch.zeros((E, N), dtype=torch.uint8, device=dev)
+        # obs / vo_count as the library last wrote them: their version counters right after that call (None: not
+        # a consistent pair, the next step writes in full).  Any in-place torch op on either tensor or a view of
+        # it bumps its counter; writers that bypass it (.data, DLPack, raw pointers) call invalidate_outputs().
+        self.reuse_obs = bool(reuse_obs)
+        self._obs_ver = None
+        self._args = _lib.StepArgs()
+        self._args.acceler = float(acceler)
         # optional float64 copy of the reward, as the reference returns it (mdin.py:28)
         self.reward64 = None
         if reward_f64:
@@ -102,22 +112,47 @@ class BatchedDroneEnv:
             raise AssertionError(f"actions must have shape ({self.E}, {self.N}, 3)")  # drone.py:101
         return a.contiguous(), (1 if a.dtype == torch.float64 else 0)
 
+    # -- observation reuse -----------------------------------------------------------
+    def invalidate_outputs(self):
+        """The next step writes obs / vo_count in full.  Needed only after writing either tensor in a way
+        torch's version counter does not see (.data, DLPack, a raw pointer, another process)."""
+        self._obs_ver = None
+
+    def _own_versions(self):
+        return (self.obs._version, self.vo_count._version)
+
+    def _touches(self, o, c):
+        """(the call writes exactly the env's own pair, it writes into the memory of either of them)"""
+        po, pc = o.data_ptr() == self.obs.data_ptr(), c.data_ptr() == self.vo_count.data_ptr()
+        return po and pc, po or pc
+
+    def _call_step(self, a, dt, policy, autoreset, o, c, name):
+        """rvo3d_step_ex into (o, c).  Into the env's own pair it passes prev_vo_count = vo_count when the pair is
+        still exactly what the library wrote (rvo3d_step_args: the zeros already there are not stored again)."""
+        own, touches = self._touches(o, c)
+        args = self._args
+        args.actions = a.data_ptr(); args.action_dtype = dt; args.policy = policy
+        args.autoreset = 1 if autoreset else 0
+        args.obs = o.data_ptr(); args.vo_count = c.data_ptr()
+        args.reward = self.reward.data_ptr(); args.done = self.done.data_ptr()
+        args.info = self.info.data_ptr(); args.finish = self.finish.data_ptr()
+        args.reset_mask = self.reset_mask.data_ptr()
+        reuse = own and self.reuse_obs and self._obs_ver is not None and self._obs_ver == self._own_versions()
+        args.prev_vo_count = c.data_ptr() if reuse else None
+        if touches:
+            self._obs_ver = None
+        _lib.check(_lib.lib().rvo3d_step_ex(self._h, C.byref(args), self._stream()), name)
+        if own:
+            self._obs_ver = self._own_versions()
+        self._last_actions = a  # keep the borrowed buffer alive until the launch ran
+
     # -- reference surface ----------------------------------------------------------
     def step(self, actions, autoreset: bool = False):
         """mdin.drone_step for every env.  Returns views of the handle-owned
         output tensors (obs f32 [E,N,W], vo_count, reward f32, done, info, finish)."""
         a, dt = self._actions(actions)
-        L = _lib.lib()
-        if autoreset:
-            rc = L.rvo3d_step_autoreset(self._h, _ptr(a), dt, _ptr(self.obs), _ptr(self.vo_count),
-                                        _ptr(self.reward), _ptr(self.done), _ptr(self.info),
-                                        _ptr(self.finish), _ptr(self.reset_mask), self._stream())
-        else:
-            rc = L.rvo3d_step(self._h, _ptr(a), dt, _ptr(self.obs), _ptr(self.vo_count),
-                              _ptr(self.reward), _ptr(self.done), _ptr(self.info),
-                              _ptr(self.finish), self._stream())
-        _lib.check(rc, "rvo3d_step")
-        self._last_actions = a  # keep the borrowed buffer alive until the launch ran
+        self._call_step(a, dt, 0, autoreset, self.obs, self.vo_count,
+                        "rvo3d_step_autoreset" if autoreset else "rvo3d_step")
         return self.obs, self.vo_count, self.reward, self.done, self.info, self.finish
 
     def step_policy(self, a_inc, autoreset: bool = True, obs_out=None, cnt_out=None):
@@ -128,12 +163,8 @@ class BatchedDroneEnv:
         if tuple(a.shape) != (self.E, self.N, 3):
             raise AssertionError(f"a_inc must have shape ({self.E}, {self.N}, 3)")
         o, c = self._outs(obs_out, cnt_out)
-        rc = _lib.lib().rvo3d_step_policy(
-            self._h, _ptr(a), C.c_float(self.acceler), _ptr(o), _ptr(c),
-            _ptr(self.reward), _ptr(self.done), _ptr(self.info), _ptr(self.finish),
-            _ptr(self.reset_mask), 1 if autoreset else 0, self._stream())
-        _lib.check(rc, "rvo3d_step_policy")
-        self._last_actions = a
+        self._args.acceler = float(self.acceler)
+        self._call_step(a, _lib.RVO3D_F32, 1, autoreset, o, c, "rvo3d_step_policy")
         return o, c, self.reward, self.done, self.info, self.finish
 
     def reset(self, env_mask=None):
@@ -152,7 +183,7 @@ class BatchedDroneEnv:
 
     def _outs(self, obs_out, cnt_out):
         """Observation outputs: the env's own tensors, or caller-provided ones (e.g. the next
-        slot of a rollout buffer: the kernel writes there directly, nothing is copied)."""
+        slot of a rollout buffer: the kernel writes there directly, nothing is copied; always in full)."""
         if obs_out is None:
             return self.obs, self.vo_count
         if (obs_out.dtype != torch.float32 or cnt_out.dtype != torch.int32 or not obs_out.is_contiguous()
@@ -163,7 +194,12 @@ class BatchedDroneEnv:
 
     def observe(self, obs_out=None, cnt_out=None):
         o, c = self._outs(obs_out, cnt_out)
+        own, touches = self._touches(o, c)
+        if touches:
+            self._obs_ver = None
         _lib.check(_lib.lib().rvo3d_observe(self._h, _ptr(o), _ptr(c), self._stream()), "rvo3d_observe")
+        if own:
+            self._obs_ver = self._own_versions()
         return o, c
 
     def des_vel(self):

@@ -140,6 +140,32 @@ int rvo3d_step_policy(rvo3d_env *h, const float *a_inc, float acceler, float *ob
                       int32_t *vo_count, float *reward, uint8_t *done, uint8_t *info,
                       uint8_t *finish, uint8_t *reset_mask, int32_t autoreset, void *stream);
 
+/* All three step entry points in one, with the arguments in a struct (HOST pointer; the pointers
+ * inside it are device pointers as above):
+ *   policy == 0: rvo3d_step (autoreset == 0) or rvo3d_step_autoreset (autoreset != 0), actions of
+ *                action_dtype;
+ *   policy != 0: rvo3d_step_policy, actions = a_inc (float32), acceler, autoreset as there.
+ * prev_vo_count (nullable) is a promise about obs: obs and prev_vo_count are a CONSISTENT PAIR - both
+ * last written by one observe / step call of this library (prev_vo_count as its vo_count output) and
+ * changed by nobody since - so every float of row r past 12 + 9 * prev_vo_count[r] is zero already.  The
+ * step then leaves out the stores of those zeros (the fused auto-reset step does; the other paths write
+ * in full).  The result is the same as with NULL, which always writes every byte.  prev_vo_count may be
+ * the vo_count output itself. */
+typedef struct rvo3d_step_args {
+  const void *actions;          /* [E][N][3]                                                    */
+  int32_t action_dtype;         /* RVO3D_F32 / RVO3D_F64 (policy: ignored, float32)             */
+  int32_t policy;               /* != 0: raw policy samples, the trainer glue of rvo3d_step_policy */
+  float acceler;                /* policy only: ir_gym.acceler                                  */
+  int32_t autoreset;            /* != 0: the fused reset protocol of rvo3d_step_autoreset       */
+  float *obs;
+  int32_t *vo_count;
+  float *reward;
+  uint8_t *done, *info, *finish;
+  uint8_t *reset_mask;          /* nullable; autoreset only                                     */
+  const int32_t *prev_vo_count; /* nullable: see above                                          */
+} rvo3d_step_args;
+int rvo3d_step_ex(rvo3d_env *h, const rvo3d_step_args *args, void *stream);
+
 /* ---- the trainer's per-step glue around the env step (train/policy/multi_ppo.py:193-281), no handle:
  * plain device pointers, work enqueued on `stream` of the current device ---- */
 
