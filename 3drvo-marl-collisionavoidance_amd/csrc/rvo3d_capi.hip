@@ -237,6 +237,21 @@ int launch_policy_mlp(const rvo3d::PolicyMlpArgs& A, unsigned grid, hipStream_t 
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
 }
+template <int KS1>
+int launch_policy_mlp_x3(const rvo3d::PolicyMlpArgs& A, unsigned grid, hipStream_t s) {
+  constexpr int lds = rvo3d::kX3LdsBytes;
+  static uint64_t attr_set = 0;  // (as launch_policy_mlp)
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !((attr_set >> dev) & 1)) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rvo3d::policy_mlp_x3_kernel<KS1, kMlpWaves>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (dev >= 0 && dev < 64) attr_set |= (uint64_t)1 << dev;
+  }
+  hipLaunchKernelGGL((rvo3d::policy_mlp_x3_kernel<KS1, kMlpWaves>), dim3(grid), dim3(64 * kMlpWaves), lds, s, A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+}
 }  // namespace
 
 // optional noise counter in device memory (rvo3d_rollout_set_step_counter): added to the `step` of every sampling launch,
@@ -765,6 +780,83 @@ int rvo3d_policy_mlp_sample(const void* blob, int32_t obs_width, const float* ob
     case 6: return launch_policy_mlp<6>(A, grid, s);
     case 7: return launch_policy_mlp<7>(A, grid, s);
     default: return launch_policy_mlp<8>(A, grid, s);
+  }
+  RVO3D_API_END
+}
+
+// The float32-class twin of the trio above (train/policy/policy_rnn_ac.py:57-69, :197-257, float32): every product of
+// the three layers is a_hi b_hi + a_lo b_hi + a_hi b_lo of bf16 halves (hi = bf16_rne(x), lo = bf16_rne(x - hi)) with
+// float32 accumulation; the first layer's bias as hi and lo against an exact 1, b2 and the head biases in float32, ReLU
+// on the float32 sums before the split; the per-row tail, the noise, vo_count and the range-checked observation reads
+// are those of rvo3d_policy_mlp_sample.  Same arguments and checks.
+int64_t rvo3d_policy_mlp_x3_blob_bytes(int32_t obs_width) {
+  if (obs_width < 1 || obs_width > 126) return -1;
+  return 2 * rvo3d::mlp_x3_net_bytes(rvo3d::mlp_ks1(obs_width));
+}
+
+int rvo3d_policy_mlp_x3_pack(const rvo3d_mlp_weights* pi, const rvo3d_mlp_weights* v, int32_t obs_width, void* blob,
+                             void* stream) {
+  RVO3D_API_BEGIN
+  if (!pi || !v || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  const rvo3d_mlp_weights* n[2] = {pi, v};
+  rvo3d::MlpPackArgs A;
+  A.k_in = obs_width; A.ks1 = rvo3d::mlp_ks1(obs_width);
+  for (int i = 0; i < 2; ++i) {
+    if (!n[i]->w1 || !n[i]->b1 || !n[i]->w2 || !n[i]->b2 || !n[i]->w3 || !n[i]->b3)
+      return fail(RVO3D_ERR_INVALID, "null weight pointer");
+    A.w1[i] = n[i]->w1; A.b1[i] = n[i]->b1; A.w2[i] = n[i]->w2; A.b2[i] = n[i]->b2; A.w3[i] = n[i]->w3; A.b3[i] = n[i]->b3;
+  }
+  A.blob = static_cast<unsigned char*>(blob);
+  hipLaunchKernelGGL(rvo3d::mlp_x3_pack_kernel, dim3(64, 2), dim3(256), 0, static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_policy_mlp_x3_sample(const void* blob, int32_t obs_width, const float* obs, int64_t obs_ld, int64_t rows,
+                               const int32_t* vo_count, int32_t state_dim, int32_t row_dim, int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed, uint64_t step,
+                               float* act, float* logp, float* val, float* dbg_mu, float* dbg_raw, void* stream) {
+  RVO3D_API_BEGIN
+  if (!blob || !obs || !log_std || !act || !logp || !val) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
+  if (rows < 0 || obs_ld < obs_width) return fail(RVO3D_ERR_INVALID, "rows < 0 or obs_ld < obs_width");
+  if (rows > 0 && ((rows - 1) * obs_ld + obs_width) * 4 > (int64_t)0x7fffffff)
+    return fail(RVO3D_ERR_INVALID, "the observation array must stay below 2 GiB per call (32-bit buffer offsets): split the rows");
+  if (reinterpret_cast<uintptr_t>(obs) & 3) return fail(RVO3D_ERR_INVALID, "obs must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  if (rows == 0) return RVO3D_OK;
+  int dev = 0, cus = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const int ks1 = rvo3d::mlp_ks1(obs_width);
+  rvo3d::PolicyMlpArgs A;
+  A.blob = static_cast<const unsigned char*>(blob); A.net_bytes = rvo3d::mlp_x3_net_bytes(ks1);
+  A.obs = obs; A.ld_obs = obs_ld; A.k_in = obs_width;
+  A.cnt = vo_count; A.state_dim = state_dim; A.row_dim = row_dim;
+  if (vo_count && (state_dim < 0 || row_dim < 1 || state_dim > obs_width))
+    return fail(RVO3D_ERR_INVALID, "vo_count needs 0 <= state_dim <= obs_width and row_dim >= 1");
+  A.S = rvo3d::PolicySampleArgs{};
+  A.S.tanh_out = tanh_out; A.S.log_std = log_std; A.S.std_factor = std_factor; A.S.seed = seed; A.S.step = step;
+  A.S.step_dev = g_step_dev.load();
+  A.S.rows = rows; A.S.act = act; A.S.logp = logp; A.S.val = val; A.S.dbg_mu = dbg_mu; A.S.dbg_raw = dbg_raw;
+  // one workgroup per CU, half of them per network; every wave takes 64 rows per trip (as rvo3d_policy_mlp_sample)
+  const int64_t nchunks = (rows + 63) / 64;
+  int64_t G = (nchunks + kMlpWaves - 1) / kMlpWaves;
+  const int64_t Gmax = cus >= 2 ? cus / 2 : 1;
+  if (G > Gmax) G = Gmax;
+  const unsigned grid = (unsigned)(2 * G);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (ks1) {
+    case 1: return launch_policy_mlp_x3<1>(A, grid, s);
+    case 2: return launch_policy_mlp_x3<2>(A, grid, s);
+    case 3: return launch_policy_mlp_x3<3>(A, grid, s);
+    case 4: return launch_policy_mlp_x3<4>(A, grid, s);
+    case 5: return launch_policy_mlp_x3<5>(A, grid, s);
+    case 6: return launch_policy_mlp_x3<6>(A, grid, s);
+    case 7: return launch_policy_mlp_x3<7>(A, grid, s);
+    default: return launch_policy_mlp_x3<8>(A, grid, s);
   }
   RVO3D_API_END
 }

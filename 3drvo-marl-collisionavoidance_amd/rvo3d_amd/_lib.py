@@ -110,7 +110,8 @@ class StateView(C.Structure):
 SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_reset",
            "rvo3d_reset_drones", "rvo3d_observe", "rvo3d_step", "rvo3d_step_autoreset",
            "rvo3d_step_policy", "rvo3d_step_ex", "rvo3d_policy_sample", "rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_pack",
-           "rvo3d_policy_mlp_sample", "rvo3d_reader_zero_features", "rvo3d_policy_rows", "rvo3d_reader_first_step", "rvo3d_rollout_account", "rvo3d_rollout_set_step_counter", "rvo3d_set_reward_f64",
+           "rvo3d_policy_mlp_sample", "rvo3d_policy_mlp_x3_blob_bytes", "rvo3d_policy_mlp_x3_pack", "rvo3d_policy_mlp_x3_sample",
+           "rvo3d_reader_zero_features", "rvo3d_policy_rows", "rvo3d_reader_first_step", "rvo3d_rollout_account", "rvo3d_rollout_set_step_counter", "rvo3d_set_reward_f64",
            "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
 
@@ -145,6 +146,10 @@ def lib():
     L.rvo3d_policy_mlp_pack.argtypes = [C.POINTER(MlpWeights), C.POINTER(MlpWeights), i32, vp, vp]
     L.rvo3d_policy_mlp_sample.argtypes = [vp, i32, vp, C.c_int64, C.c_int64, vp, i32, i32, i32, vp, C.c_float,
                                           C.c_uint64, C.c_uint64] + [vp] * 6
+    L.rvo3d_policy_mlp_x3_blob_bytes.argtypes = [i32]
+    L.rvo3d_policy_mlp_x3_blob_bytes.restype = C.c_int64
+    L.rvo3d_policy_mlp_x3_pack.argtypes = L.rvo3d_policy_mlp_pack.argtypes
+    L.rvo3d_policy_mlp_x3_sample.argtypes = L.rvo3d_policy_mlp_sample.argtypes
     L.rvo3d_reader_zero_features.argtypes = [vp, C.c_int64, C.c_int64, i32, i32, vp, vp, C.c_float, C.c_float, C.c_float,
                                              vp, C.c_int64, vp, vp, vp, vp]
     L.rvo3d_policy_rows.argtypes = [C.POINTER(RnnPolicy), vp, C.c_int64, vp, vp, vp, vp, i32, vp, C.c_float, C.c_uint64,

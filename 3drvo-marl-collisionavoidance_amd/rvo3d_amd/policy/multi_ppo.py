@@ -155,7 +155,7 @@ class multi_ppo:
                  save_result=False, counter=0, test_env=None, lr_decay_epoch=1000,
                  max_update_num=None, mpi=False, figure_save_path=None, minibatch_size=None,
                  dist=None, sanitize_rewards=True, amp=False, reference_order=False, fused_rollout=True,
-                 rollout_chunk=None, tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, **kwargs):
+                 rollout_chunk=None, tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False, **kwargs):
         np.random.seed(seed)
         self.env, self.ac, self.dist = env, ac_policy, dist
         # The agent order of the reference-order update comes from a generator of its own, seeded like
@@ -168,6 +168,11 @@ class multi_ppo:
         # bf16 rollouts of the MLP(256, 256) actor-critic: the policy step as ONE matrix-core kernel
         # (rvo3d_policy_mlp_sample) instead of cast + three library GEMMs + rvo3d_policy_sample
         self.fused_mlp = bool(fused_mlp)
+        # float32 rollouts (amp=False) of the same actor-critic through the split-bf16 twin of that kernel
+        # (rvo3d_policy_mlp_x3_sample, float32-class products) instead of float32 GEMMs + rvo3d_policy_sample; opt-in
+        if amp and fused_mlp_fp32:
+            raise ValueError("fused_mlp_fp32=True is the float32 rollout's kernel: it needs amp=False")
+        self.fused_mlp_fp32 = bool(fused_mlp_fp32)
         # the fast paths' per-step launches replayed as HIP graphs from the second rollout on (see _collect_fused);
         # opt-in: measured at 64 x 4096, 0.158 ms per step with and 0.157-0.161 without - the gaps between the dependent
         # kernels of a graph are what they are between stream launches
@@ -227,7 +232,8 @@ class multi_ppo:
     def _fused_mode(self):
         """How a rollout step runs on the GPU: "mlp" - config 3's MLP(256, 256) actor-critic in reduced precision:
         the whole policy step (cast, hidden layers, heads, sampling, stores) is ONE kernel on the matrix cores,
-        rvo3d_policy_mlp_sample; "heads" - other MLP actor-critics (and float32): library GEMMs up to the last
+        rvo3d_policy_mlp_sample; "mlp_x3" - the same in a float32 rollout (amp=False, fused_mlp_fp32=True): the
+        split-bf16 kernel rvo3d_policy_mlp_x3_sample, float32-class products; "heads" - other MLP actor-critics (and float32): library GEMMs up to the last
         hidden layers, everything from there on in rvo3d_policy_sample; "rnn0" - the reference's biGRU actor-critic with
         (256, 256) heads in reduced precision: rows without a velocity-obstacle row (nearly all) through the collapsed
         first layer, rvo3d_reader_zero_features + rvo3d_policy_mlp_sample, the others through the "heads" / "direct" path
@@ -238,6 +244,9 @@ class multi_ppo:
             return None
         if self.amp and self.fused_mlp and hasattr(self.ac, "mlp_blob") and self.ac.mlp_blob() is not None:
             return "mlp"
+        if (not self.amp and self.fused_mlp and self.fused_mlp_fp32 and hasattr(self.ac, "mlp_blob")
+                and self.ac.mlp_blob("x3") is not None):
+            return "mlp_x3"
         if (self.amp and self.fused_mlp and not getattr(self, "_rnn0_dense", False) and hasattr(self.ac, "zero_vo_plan")
                 and self.ac.zero_vo_plan() is not None and self.ac.zero_vo_plan()["rows_net"] is not None):
             return "rnn0"
@@ -298,7 +307,8 @@ class multi_ppo:
         rollouts), the policy GEMMs up to the last hidden layers (mlp_ac.hidden_pair), rvo3d_policy_sample
         (heads, tanh, sample, log-probability, np.round(a, 2), the three buffer stores), the env step from
         the stored action, rvo3d_rollout_account (reward slot, episode counters, path cuts, who still
-        needs a reset).  Same semantics as collect(): multi_ppo.py:183-281."""
+        needs a reset).  Same semantics as collect(): multi_ppo.py:183-281.  graph_rollout=True replays the
+        "mlp" and "rnn0" modes only; every other mode ("mlp_x3" included) launches eagerly."""
         import ctypes as C
         from .. import _lib
         env, buf, L = self.env, self.buf, _lib.lib()
@@ -321,11 +331,13 @@ class multi_ppo:
         since_full_reset = 0
         mode = self._fused_mode()
         log_std = self.ac.log_std
-        mb = self.ac.mlp_blob() if mode == "mlp" else None  # (once per rollout: the weights do not change inside it)
+        # (once per rollout: the weights do not change inside it)
+        mb = self.ac.mlp_blob() if mode == "mlp" else self.ac.mlp_blob("x3") if mode == "mlp_x3" else None
         zp = self.ac.zero_vo_plan() if mode == "rnn0" else None
         if mode == "rnn0" and "vo_count" in ac:
             ac["vo_count"].zero_()  # (the kernels leave it at zero; a rollout that was interrupted half-way may not have)
-        # Graph replay (graph_rollout=True; the MLP and biGRU fast paths): the launches of step t - every argument by value,
+        # Graph replay (graph_rollout=True; the bf16 MLP and biGRU fast paths, "mlp" / "rnn0" only - "mlp_x3" and the
+        # others always launch eagerly): the launches of step t - every argument by value,
         # every buffer slot at a fixed address - are captured once per slot into a HIP graph and replayed in later
         # epochs (the loop's wall time exceeds its GPU time by the dispatch gaps between three to five dependent
         # launches; measured: a graph's kernels keep those gaps - no gain, hence opt-in).  The noise counter then lives in device memory
@@ -344,12 +356,13 @@ class multi_ppo:
         def launches(t, epoch_ended):
             x = buf.obs[t].view(E * N, env.W)
             act_t, logp_t, val_t = buf.act[t].view(E * N, 3), buf.logp[t].view(E * N), buf.val[t].view(E * N)
-            if mode == "mlp":
+            if mode in ("mlp", "mlp_x3"):
                 # (the env's counts: column groups that are zero for all rows of a wave are skipped)
-                _lib.check(L.rvo3d_policy_mlp_sample(p(mb["blob"]), env.W, p(x), x.stride(0), E * N,
-                                                     p(buf.cnt[t]), 12, 9, 1 if mb["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
-                                                     step_arg(), p(act_t), p(logp_t), p(val_t), None, None, stream()),
-                           "rvo3d_policy_mlp_sample")
+                fn = L.rvo3d_policy_mlp_sample if mode == "mlp" else L.rvo3d_policy_mlp_x3_sample
+                _lib.check(fn(p(mb["blob"]), env.W, p(x), x.stride(0), E * N,
+                              p(buf.cnt[t]), 12, 9, 1 if mb["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
+                              step_arg(), p(act_t), p(logp_t), p(val_t), None, None, stream()),
+                           "rvo3d_policy_mlp_sample" if mode == "mlp" else "rvo3d_policy_mlp_x3_sample")
                 ac["step"] += 1
             if mode == "rnn0":
                 # rows without a velocity-obstacle row: collapsed first layer (rvo3d_reader_zero_features builds its 20

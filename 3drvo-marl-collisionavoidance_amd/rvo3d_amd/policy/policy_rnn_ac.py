@@ -577,10 +577,14 @@ class mlp_ac(nn.Module):
         the module path)."""
         return _plan_cached(self, dtype, lambda: _mlp_pair_plan(self.pi_net, self.v_net, dtype))
 
-    def mlp_blob(self):
+    def mlp_blob(self, precision="bf16"):
         """The packed weights of rvo3d_policy_mlp_sample (the whole policy step in ONE kernel on the matrix cores:
         csrc/rvo3d_policy_mlp.hpp), repacked when a parameter changed; None when this is not the shape that kernel
-        is written for - ReLU MLPs obs_width -> 256 -> 256 -> 3 (Tanh or Identity) / -> 1, obs_width <= 126, on a GPU."""
+        is written for - ReLU MLPs obs_width -> 256 -> 256 -> 3 (Tanh or Identity) / -> 1, obs_width <= 126, on a GPU.
+        precision="x3": the blob of rvo3d_policy_mlp_x3_sample (split-bf16 products, float32-class:
+        csrc/rvo3d_policy_mlp_x3.hpp).  Each precision has its own cache entry."""
+        if precision not in ("bf16", "x3"):
+            raise ValueError(f"precision must be 'bf16' or 'x3', not {precision!r}")
         pl = [m for m in self.pi_net if isinstance(m, nn.Linear)]
         vl = [m for m in self.v_net if isinstance(m, nn.Linear)]
         pa = [m for m in self.pi_net if not isinstance(m, nn.Linear)]
@@ -593,24 +597,27 @@ class mlp_ac(nn.Module):
             return None
         params = list(self.pi_net.parameters()) + list(self.v_net.parameters())
         key = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
-        hit = getattr(self, "_blob", None)
+        attr = "_blob" if precision == "bf16" else "_blob_x3"
+        hit = getattr(self, attr, None)
         if hit is not None and hit[0] == key:
             return hit[1]
         import ctypes as C
         from .. import _lib
         L = _lib.lib()
+        nbytes = L.rvo3d_policy_mlp_blob_bytes if precision == "bf16" else L.rvo3d_policy_mlp_x3_blob_bytes
+        pack = L.rvo3d_policy_mlp_pack if precision == "bf16" else L.rvo3d_policy_mlp_x3_pack
         dev = pl[0].weight.device
-        blob = hit[1]["blob"] if hit is not None else torch.empty(int(L.rvo3d_policy_mlp_blob_bytes(self.obs_width)),
-                                                                   dtype=torch.uint8, device=dev)
+        blob = hit[1]["blob"] if hit is not None else torch.empty(int(nbytes(self.obs_width)), dtype=torch.uint8,
+                                                                   device=dev)
         keep = [t.detach().contiguous() for lin in (pl, vl) for m in lin for t in (m.weight, m.bias)]
         a = _lib.MlpWeights(*[t.data_ptr() for t in keep[:6]])
         b = _lib.MlpWeights(*[t.data_ptr() for t in keep[6:]])
         with torch.cuda.device(dev):
-            _lib.check(L.rvo3d_policy_mlp_pack(C.byref(a), C.byref(b), self.obs_width, C.c_void_p(blob.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                       "rvo3d_policy_mlp_pack")
+            _lib.check(pack(C.byref(a), C.byref(b), self.obs_width, C.c_void_p(blob.data_ptr()),
+                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                       "rvo3d_policy_mlp_pack" if precision == "bf16" else "rvo3d_policy_mlp_x3_pack")
         out = dict(blob=blob, tanh=isinstance(pa[-1], nn.Tanh))
-        self._blob = (key, out)
+        setattr(self, attr, (key, out))
         return out
 
     def prepare_input(self, obs, cnt, plan, cache):

@@ -215,6 +215,23 @@ int rvo3d_policy_mlp_sample(const void *blob, int32_t obs_width, const float *ob
                             const int32_t *vo_count, int32_t state_dim, int32_t row_dim, int32_t tanh_out, const float *log_std, float std_factor, uint64_t seed, uint64_t step,
                             float *act, float *logp, float *val, float *dbg_mu, float *dbg_raw, void *stream);
 
+/* The same policy step at float32-class precision (the reference's policy is float32: train/policy/policy_rnn_ac.py:57-69,
+ * :197-235, :238-257).  Every product of the three layers - observation x W1, H1 x W2, H2 x W3 - is split bf16,
+ * a_hi b_hi + a_lo b_hi + a_hi b_lo with hi = bf16_rne(x), lo = bf16_rne(x - hi), accumulated in float32 on the matrix
+ * cores (the dropped a_lo b_lo is below 2^-16 of each product).  The first layer's bias rides as hi and lo in the
+ * weight column obs_width against an exact 1; the second layer's and the heads' biases enter as float32; ReLU acts on
+ * the float32 sums and the result is split after it.  Everything else - the per-row tail (tanh, Philox noise with
+ * counter (row, step): the same noise as rvo3d_policy_sample and rvo3d_policy_mlp_sample for the same seed and step,
+ * log-probability, np.round(a, 2), the stores), vo_count (bit-identical to NULL), the range-checked observation reads,
+ * the arguments and their checks - is rvo3d_policy_mlp_sample's.  The blob has its own layout and size
+ * (rvo3d_policy_mlp_x3_blob_bytes); repack after every optimizer step. */
+int64_t rvo3d_policy_mlp_x3_blob_bytes(int32_t obs_width);
+int rvo3d_policy_mlp_x3_pack(const rvo3d_mlp_weights *pi, const rvo3d_mlp_weights *v, int32_t obs_width, void *blob,
+                             void *stream);
+int rvo3d_policy_mlp_x3_sample(const void *blob, int32_t obs_width, const float *obs, int64_t obs_ld, int64_t rows,
+                               const int32_t *vo_count, int32_t state_dim, int32_t row_dim, int32_t tanh_out, const float *log_std, float std_factor, uint64_t seed, uint64_t step,
+                               float *act, float *logp, float *val, float *dbg_mu, float *dbg_raw, void *stream);
+
 /* The reader's features (rnn_Reader.obs_rnn + LayerNorm, train/policy/policy_rnn_ac.py:75-127) of rows WITHOUT a
  * velocity-obstacle row, in collapsed form.  The GRU of such a row sees a zero input from h = 0: its hidden state h0 is
  * the same for every row, and LayerNorm(concat(p, h0)) depends on the row only through mean and rstd, so a linear

@@ -16,6 +16,8 @@ ap.add_argument("--steps", type=int, default=16)
 ap.add_argument("--policy", default="mlp")
 ap.add_argument("--minibatch", type=int, default=262144)
 ap.add_argument("--amp", action="store_true")
+ap.add_argument("--fp32-kernel", action="store_true", help="float32 rollout through the split-bf16 policy kernel "
+                "(multi_ppo(fused_mlp_fp32=True): mode mlp_x3) instead of float32 GEMMs + the heads kernel")
 ap.add_argument("--no-update", action="store_true", help="rollout only (for profiling the loop)")
 ap.add_argument("--no-tune", action="store_true", help="hipBLASLt's heuristic kernels instead of TunableOp's pick "
                 "(a rocprofv3 trace then holds no tuning runs; the GEMMs are ~15 %% slower)")
@@ -32,7 +34,8 @@ ac = (mlp_ac(env.W) if args.policy == "mlp" else
       rnn_ac(None, Space(), 12, 9, 256, (256, 256), (256, 256), torch.nn.ReLU, torch.nn.Tanh,
              torch.nn.Identity, use_gpu=False, rnn_mode="biGRU")).cuda()
 tr = multi_ppo(env, ac, train_epoch=0, steps_per_epoch=T, max_ep_len=500, train_pi_iters=2,
-               train_v_iters=2, target_kl=1e9, minibatch_size=args.minibatch, save_freq=10**9, amp=args.amp, tune_gemms=not args.no_tune)
+               train_v_iters=2, target_kl=1e9, minibatch_size=args.minibatch, save_freq=10**9, amp=args.amp, tune_gemms=not args.no_tune,
+               fused_mlp_fp32=args.fp32_kernel)
 env.reset(); env.observe()
 tr.collect(); tr.buf.get()            # warm-up (allocator, hipBLASLt heuristics)
 torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -43,7 +46,7 @@ torch.cuda.synchronize(); t2 = time.perf_counter()
 if not args.no_update:
     tr.update(data)
 torch.cuda.synchronize(); t3 = time.perf_counter()
-print(json.dumps({"policy": args.policy, "amp": args.amp, "envs": E, "drones": N, "steps": T,
+print(json.dumps({"policy": args.policy, "amp": args.amp, "mode": tr._fused_mode(), "envs": E, "drones": N, "steps": T,
                   "rollout_drone_steps_per_s": E * N * T / (t1 - t0),
                   "rollout_ms_per_step": (t1 - t0) / T * 1e3, "gae_ms": (t2 - t1) * 1e3,
                   "update_s": t3 - t2,

@@ -3,7 +3,7 @@
 # env_kernel instantiation as the compiler reports them (-Rpass-analysis=kernel-resource-usage)
 cd "$(dirname "$0")/.."
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 \
-  -Rpass-analysis=kernel-resource-usage "$@" -o /tmp/rvo3d_ru.so \
+  -Rpass-analysis=kernel-resource-usage "$@" -o ${RU_OUT:-/tmp/rvo3d_ru.so} \
   3drvo-marl-collisionavoidance_amd/csrc/rvo3d_capi.hip 2>&1 | python3 -c "
 import re, sys
 cur = None; rows = {}
