@@ -252,6 +252,24 @@ int launch_policy_mlp_x3(const rvo3d::PolicyMlpArgs& A, unsigned grid, hipStream
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
 }
+template <int H, int ND>
+int launch_policy_rnn_tiles(const rvo3d::RnnTilesArgs& A, unsigned grid, hipStream_t s) {
+  constexpr int lds = rvo3d::kRnnTilesWaves * H * 128;  // the running hidden state, 128 H bytes per wave
+  static uint64_t attr_set = 0;  // (as launch_policy_mlp)
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !((attr_set >> dev) & 1)) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rvo3d::policy_rnn_tiles_kernel<H, ND>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (dev >= 0 && dev < 64) attr_set |= (uint64_t)1 << dev;
+  }
+  hipLaunchKernelGGL((rvo3d::policy_rnn_tiles_kernel<H, ND>), dim3(grid), dim3(64 * rvo3d::kRnnTilesWaves), lds, s, A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+}
+bool rnn_tiles_shape_ok(int32_t hidden, int32_t in_dim, int32_t state_dim) {
+  return (hidden == 64 || hidden == 256) && in_dim == 9 && state_dim >= 1 && state_dim <= 16;
+}
 }  // namespace
 
 // optional noise counter in device memory (rvo3d_rollout_set_step_counter): added to the `step` of every sampling launch,
@@ -918,6 +936,85 @@ int rvo3d_policy_rows(const rvo3d_rnn_policy* net, const float* obs, int64_t obs
   hipLaunchKernelGGL(rvo3d::policy_rows_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
+  RVO3D_API_END
+}
+
+// The biGRU policy step of the listed rows in 32-row MFMA tiles (csrc/rvo3d_policy_rnn_tiles.hpp): a bucket launch sorts
+// the list into per-count sub-lists, a persistent launch runs the tiles.
+int64_t rvo3d_policy_rnn_tiles_blob_bytes(int32_t hidden, int32_t in_dim, int32_t state_dim, int32_t bidir) {
+  if (!rnn_tiles_shape_ok(hidden, in_dim, state_dim)) return -1;
+  return rvo3d::rnn_tiles_layout(hidden, bidir ? 2 : 1).total;
+}
+
+int64_t rvo3d_policy_rnn_tiles_work_bytes(int64_t max_rows, int32_t slots) {
+  if (max_rows < 1 || slots < 1 || slots > rvo3d::kRnnTilesMaxSlots) return -1;
+  return 4 * (rvo3d::kRnnTilesWorkHeader + (int64_t)slots * max_rows);
+}
+
+int rvo3d_policy_rnn_tiles_pack(const rvo3d_rnn_policy* net, void* blob, int64_t blob_bytes, void* stream) {
+  RVO3D_API_BEGIN
+  if (!net || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (!net->w_ih_f || !net->w_hh_f || !net->b_ih_f || !net->b_hh_f || !net->ln_w || !net->ln_b)
+    return fail(RVO3D_ERR_INVALID, "null reader weight");
+  const bool bi = net->w_ih_r != nullptr;
+  if (bi != (net->w_hh_r != nullptr) || bi != (net->b_ih_r != nullptr) || bi != (net->b_hh_r != nullptr))
+    return fail(RVO3D_ERR_INVALID, "the reverse direction needs all four of w_ih_r / w_hh_r / b_ih_r / b_hh_r");
+  if (!rnn_tiles_shape_ok(net->hidden, net->in_dim, net->state_dim))
+    return fail(RVO3D_ERR_INVALID, "rnn tiles: hidden must be 64 or 256, in_dim 9, state_dim 1..16");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  if (blob_bytes != rvo3d_policy_rnn_tiles_blob_bytes(net->hidden, net->in_dim, net->state_dim, bi))
+    return fail(RVO3D_ERR_INVALID, "blob_bytes does not match rvo3d_policy_rnn_tiles_blob_bytes for this shape");
+  const rvo3d_mlp_weights* m[2] = {&net->pi, &net->v};
+  rvo3d::RnnTilesPackArgs A;
+  A.H = net->hidden; A.ND = bi ? 2 : 1; A.SD = net->state_dim; A.IN = net->in_dim; A.eps = net->ln_eps;
+  A.w_ih[0] = net->w_ih_f; A.w_hh[0] = net->w_hh_f; A.b_ih[0] = net->b_ih_f; A.b_hh[0] = net->b_hh_f;
+  A.w_ih[1] = net->w_ih_r; A.w_hh[1] = net->w_hh_r; A.b_ih[1] = net->b_ih_r; A.b_hh[1] = net->b_hh_r;
+  A.ln_w = net->ln_w; A.ln_b = net->ln_b;
+  for (int i = 0; i < 2; ++i) {
+    if (!m[i]->w1 || !m[i]->b1 || !m[i]->w2 || !m[i]->b2 || !m[i]->w3 || !m[i]->b3)
+      return fail(RVO3D_ERR_INVALID, "null head weight");
+    A.w1[i] = m[i]->w1; A.b1[i] = m[i]->b1; A.w2[i] = m[i]->w2; A.b2[i] = m[i]->b2; A.w3[i] = m[i]->w3; A.b3[i] = m[i]->b3;
+  }
+  A.blob = static_cast<unsigned char*>(blob);
+  hipLaunchKernelGGL(rvo3d::rnn_tiles_pack_kernel, dim3(128), dim3(256), 0, static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_policy_rnn_tiles(const void* blob, int64_t blob_bytes, int32_t hidden, int32_t in_dim, int32_t state_dim,
+                           int32_t bidir, const float* obs, int64_t obs_ld, const int32_t* vo_count, const int32_t* list,
+                           int32_t* count, int32_t* done_blocks, int32_t* work, int64_t max_rows, int32_t slots,
+                           int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed, uint64_t step,
+                           float* act, float* logp, float* val, float* dbg_mu, void* stream) {
+  RVO3D_API_BEGIN
+  if (!blob || !obs || !vo_count || !list || !count || !done_blocks || !work || !log_std || !act || !logp || !val)
+    return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (!rnn_tiles_shape_ok(hidden, in_dim, state_dim))
+    return fail(RVO3D_ERR_INVALID, "rnn tiles: hidden must be 64 or 256, in_dim 9, state_dim 1..16");
+  if (slots < 1 || slots > rvo3d::kRnnTilesMaxSlots) return fail(RVO3D_ERR_INVALID, "slots must be 1..12");
+  if (blob_bytes != rvo3d_policy_rnn_tiles_blob_bytes(hidden, in_dim, state_dim, bidir))
+    return fail(RVO3D_ERR_INVALID, "blob_bytes does not match this shape: the blob was packed for another one");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  if (max_rows < 1 || max_rows > 0x7fffffff) return fail(RVO3D_ERR_INVALID, "max_rows must be 1..2^31-1");
+  if (obs_ld < state_dim + slots * in_dim) return fail(RVO3D_ERR_INVALID, "obs_ld < state_dim + slots * in_dim");
+  int dev = 0, cus = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  rvo3d::RnnTilesArgs A;
+  A.blob = static_cast<const unsigned char*>(blob);
+  A.obs = obs; A.obs_ld = obs_ld; A.cnt = vo_count; A.list = list; A.count = count; A.done_blocks = done_blocks;
+  A.work = work; A.max_rows = max_rows; A.SD = state_dim; A.slots = slots;
+  A.S = rvo3d::PolicySampleArgs{};
+  A.S.tanh_out = tanh_out; A.S.log_std = log_std; A.S.std_factor = std_factor; A.S.seed = seed; A.S.step = step;
+  A.S.step_dev = nullptr;  // (never graph-replayed: the noise counter is `step` alone)
+  A.S.act = act; A.S.logp = logp; A.S.val = val; A.S.dbg_mu = dbg_mu;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rvo3d::rnn_tiles_bucket_kernel, dim3(256), dim3(256), 0, s, A);
+  HIP_TRY(hipGetLastError());
+  const unsigned grid = (unsigned)(cus > 0 ? cus : 1);  // one workgroup (four independent waves) per CU, persistent
+  if (hidden == 64) return bidir ? launch_policy_rnn_tiles<64, 2>(A, grid, s) : launch_policy_rnn_tiles<64, 1>(A, grid, s);
+  return bidir ? launch_policy_rnn_tiles<256, 2>(A, grid, s) : launch_policy_rnn_tiles<256, 1>(A, grid, s);
   RVO3D_API_END
 }
 

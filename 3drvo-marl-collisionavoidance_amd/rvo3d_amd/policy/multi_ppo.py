@@ -155,7 +155,8 @@ class multi_ppo:
                  save_result=False, counter=0, test_env=None, lr_decay_epoch=1000,
                  max_update_num=None, mpi=False, figure_save_path=None, minibatch_size=None,
                  dist=None, sanitize_rewards=True, amp=False, reference_order=False, fused_rollout=True,
-                 rollout_chunk=None, tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False, **kwargs):
+                 rollout_chunk=None, tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False,
+                 fused_rnn_tiles=False, **kwargs):
         np.random.seed(seed)
         self.env, self.ac, self.dist = env, ac_policy, dist
         # The agent order of the reference-order update comes from a generator of its own, seeded like
@@ -173,6 +174,18 @@ class multi_ppo:
         if amp and fused_mlp_fp32:
             raise ValueError("fused_mlp_fp32=True is the float32 rollout's kernel: it needs amp=False")
         self.fused_mlp_fp32 = bool(fused_mlp_fp32)
+        # bf16 rollouts of the biGRU actor-critic in worlds where many drones have velocity-obstacle rows: mode
+        # "rnn_tiles" - the "rnn0" launches with the rows that have VO rows in 32-row MFMA tiles (rvo3d_policy_rnn_tiles)
+        # instead of one workgroup per row, whatever their density (no switch to "heads"); opt-in, eager launches only
+        if fused_rnn_tiles:
+            if not amp:
+                raise ValueError("fused_rnn_tiles=True is a bf16 rollout kernel: it needs amp=True")
+            zp = ac_policy.zero_vo_plan() if hasattr(ac_policy, "zero_vo_plan") else None
+            if (not hasattr(ac_policy, "rnn_tiles_blob") or zp is None or ac_policy.rnn_tiles_blob() is None
+                    or (env.W - zp["state_dim"]) % 9 or not 1 <= (env.W - zp["state_dim"]) // 9 <= 12):
+                raise ValueError("fused_rnn_tiles=True needs an rnn_ac with a shared GRU / biGRU reader of hidden 64 or "
+                                 "256, in_dim 9, state_dim <= 16, (256, 256) ReLU heads, on a GPU, and 1..12 VO slots")
+        self.fused_rnn_tiles = bool(fused_rnn_tiles)
         # the fast paths' per-step launches replayed as HIP graphs from the second rollout on (see _collect_fused);
         # opt-in: measured at 64 x 4096, 0.158 ms per step with and 0.157-0.161 without - the gaps between the dependent
         # kernels of a graph are what they are between stream launches
@@ -237,11 +250,14 @@ class multi_ppo:
         hidden layers, everything from there on in rvo3d_policy_sample; "rnn0" - the reference's biGRU actor-critic with
         (256, 256) heads in reduced precision: rows without a velocity-obstacle row (nearly all) through the collapsed
         first layer, rvo3d_reader_zero_features + rvo3d_policy_mlp_sample, the others through the "heads" / "direct" path
-        on a gathered batch; "direct" - any other actor-critic with the reference's surface
-        (`ac.pi._distribution`, `ac.v`, e.g. the biGRU rnn_ac): its own forward gives mu and v, the kernel
-        samples / rounds / stores; None - the module path of collect() (CPU, or fused_rollout=False)."""
+        on a gathered batch; "rnn_tiles" - the same actor-critic with fused_rnn_tiles=True: the "rnn0" launches with the
+        rows that do have VO rows in 32-row MFMA tiles (rvo3d_policy_rnn_tiles), at any density; "direct" - any other
+        actor-critic with the reference's surface (`ac.pi._distribution`, `ac.v`, e.g. the biGRU rnn_ac): its own forward
+        gives mu and v, the kernel samples / rounds / stores; None - the module path of collect() (CPU, or fused_rollout=False)."""
         if self.device.type != "cuda" or not self.fused_rollout:
             return None
+        if self.amp and getattr(self, "fused_rnn_tiles", False):
+            return "rnn_tiles"
         if self.amp and self.fused_mlp and hasattr(self.ac, "mlp_blob") and self.ac.mlp_blob() is not None:
             return "mlp"
         if (not self.amp and self.fused_mlp and self.fused_mlp_fp32 and hasattr(self.ac, "mlp_blob")
@@ -333,9 +349,12 @@ class multi_ppo:
         log_std = self.ac.log_std
         # (once per rollout: the weights do not change inside it)
         mb = self.ac.mlp_blob() if mode == "mlp" else self.ac.mlp_blob("x3") if mode == "mlp_x3" else None
-        zp = self.ac.zero_vo_plan() if mode == "rnn0" else None
-        if mode == "rnn0" and "vo_count" in ac:
+        zp = self.ac.zero_vo_plan() if mode in ("rnn0", "rnn_tiles") else None
+        tb = self.ac.rnn_tiles_blob() if mode == "rnn_tiles" else None
+        if mode in ("rnn0", "rnn_tiles") and "vo_count" in ac:
             ac["vo_count"].zero_()  # (the kernels leave it at zero; a rollout that was interrupted half-way may not have)
+        if mode == "rnn_tiles" and "tiles_work" in ac:
+            ac["tiles_work"][:32].zero_()  # (the sub-lists' cursors: likewise)
         # Graph replay (graph_rollout=True; the bf16 MLP and biGRU fast paths, "mlp" / "rnn0" only - "mlp_x3" and the
         # others always launch eagerly): the launches of step t - every argument by value,
         # every buffer slot at a fixed address - are captured once per slot into a HIP graph and replayed in later
@@ -364,7 +383,7 @@ class multi_ppo:
                               step_arg(), p(act_t), p(logp_t), p(val_t), None, None, stream()),
                            "rvo3d_policy_mlp_sample" if mode == "mlp" else "rvo3d_policy_mlp_x3_sample")
                 ac["step"] += 1
-            if mode == "rnn0":
+            if mode in ("rnn0", "rnn_tiles"):
                 # rows without a velocity-obstacle row: collapsed first layer (rvo3d_reader_zero_features builds its 20
                 # inputs and lists the rows that do have VO rows) + the MFMA kernel; the listed rows: one workgroup each,
                 # as the modules compute them; no host synchronisation
@@ -381,12 +400,24 @@ class multi_ppo:
                                                      1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
                                                      step_arg(), p(act_t), p(logp_t), p(val_t), None, None, stream()),
                            "rvo3d_policy_mlp_sample")
-                net = zp["rows_net"]
-                net.slots = env.nm if hasattr(env, "nm") else (env.W - zp["state_dim"]) // 9
-                _lib.check(L.rvo3d_policy_rows(C.byref(net), p(x), x.stride(0), p(cnt_t), p(ac["vo_list"]),
-                                               p(ac["vo_count"]), C.c_void_p(ac["vo_count"].data_ptr() + 4),
-                                               1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(),
-                                               p(act_t), p(logp_t), p(val_t), stream()), "rvo3d_policy_rows")
+                slots = env.nm if hasattr(env, "nm") else (env.W - zp["state_dim"]) // 9
+                if mode == "rnn_tiles":
+                    # the listed rows in 32-row MFMA tiles, grouped by their VO count on the device
+                    nw = int(L.rvo3d_policy_rnn_tiles_work_bytes(E * N, slots)) // 4
+                    if "tiles_work" not in ac or ac["tiles_work"].numel() != nw:
+                        ac["tiles_work"] = torch.zeros(nw, dtype=torch.int32, device=self.device)
+                    _lib.check(L.rvo3d_policy_rnn_tiles(
+                        p(tb["blob"]), tb["blob_bytes"], tb["hidden"], tb["in_dim"], tb["state_dim"], tb["bidir"], p(x),
+                        x.stride(0), p(cnt_t), p(ac["vo_list"]), p(ac["vo_count"]), C.c_void_p(ac["vo_count"].data_ptr() + 4),
+                        p(ac["tiles_work"]), E * N, slots, 1 if tb["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
+                        step_arg(), p(act_t), p(logp_t), p(val_t), None, stream()), "rvo3d_policy_rnn_tiles")
+                else:
+                    net = zp["rows_net"]
+                    net.slots = slots
+                    _lib.check(L.rvo3d_policy_rows(C.byref(net), p(x), x.stride(0), p(cnt_t), p(ac["vo_list"]),
+                                                   p(ac["vo_count"]), C.c_void_p(ac["vo_count"].data_ptr() + 4),
+                                                   1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(),
+                                                   p(act_t), p(logp_t), p(val_t), stream()), "rvo3d_policy_rows")
                 ac["step"] += 1
             if mode == "direct":
                 mu, v = self._mu_v(x, buf.cnt[t].view(E * N))

@@ -461,6 +461,61 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
         self._zero_plan = (key, out)
         return out
 
+    def rnn_tiles_blob(self):
+        """The packed weights of rvo3d_policy_rnn_tiles (the policy step of the rows WITH velocity-obstacle rows in 32-row
+        MFMA tiles: csrc/rvo3d_policy_rnn_tiles.hpp) with the shape that call needs: dict(blob, blob_bytes, hidden, in_dim,
+        state_dim, bidir, tanh).  Its own cache entry, repacked when a parameter changed (version or storage); None when
+        the architecture does not fit - a shared GRU / biGRU reader of hidden 64 or 256, in_dim 9, state_dim <= 16, ReLU
+        (256, 256) stacks with 3 (Tanh or Identity) / 1 outputs, float32 parameters on a GPU."""
+        r = self.pi.rnn_reader
+        if (r is None or r is not self.v.rnn_reader or r.mode not in ("GRU", "biGRU") or r.hidden_dim not in (64, 256)
+                or r.input_dim != 9 or not 1 <= r.state_dim <= 16 or next(self.parameters()).device.type != "cuda"):
+            return None
+        nets = (self.pi.net_out, self.v.v_net)
+        lins = [[m for m in n if isinstance(m, nn.Linear)] for n in nets]
+        acts = [[m for m in n if not isinstance(m, nn.Linear)] for n in nets]
+        D = r.state_dim + r.hidden_dim
+        if (any(len(l) != 3 for l in lins) or [m.out_features for m in lins[0]] != [256, 256, 3]
+                or [m.out_features for m in lins[1]] != [256, 256, 1] or any(l[0].in_features != D for l in lins)
+                or any(len(a) != 3 for a in acts)
+                or not all(isinstance(m, nn.ReLU) for a in acts for m in a[:-1])
+                or not isinstance(acts[0][-1], (nn.Tanh, nn.Identity)) or not isinstance(acts[1][-1], nn.Identity)
+                or any(m.bias is None for l in lins for m in l)
+                or any(p.dtype != torch.float32 for p in self.parameters())):
+            return None
+        params = list(self.parameters())
+        key = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
+        hit = getattr(self, "_tiles_blob", None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        import ctypes as C
+        from .. import _lib
+        L = _lib.lib()
+        bi = r.mode == "biGRU"
+        nbytes = int(L.rvo3d_policy_rnn_tiles_blob_bytes(r.hidden_dim, r.input_dim, r.state_dim, 1 if bi else 0))
+        dev = params[0].device
+        blob = hit[1]["blob"] if hit is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        g = r.rnn_net
+        keep = [t.detach().contiguous() for t in (
+            g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0) + ((
+            g.weight_ih_l0_reverse, g.weight_hh_l0_reverse, g.bias_ih_l0_reverse, g.bias_hh_l0_reverse) if bi else ()) + (
+            r.ln.weight, r.ln.bias)]
+        heads = [t.detach().contiguous() for l in lins for m in l for t in (m.weight, m.bias)]
+        ptr = [t.data_ptr() for t in keep]
+        rev = ptr[4:8] if bi else [None] * 4
+        net = _lib.RnnPolicy(*ptr[:4], *rev, *ptr[-2:], r.hidden_dim, r.input_dim, r.state_dim, 0, float(r.ln.eps), 0,
+                             _lib.MlpWeights(*[t.data_ptr() for t in heads[:6]]),
+                             _lib.MlpWeights(*[t.data_ptr() for t in heads[6:]]))
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            _lib.check(L.rvo3d_policy_rnn_tiles_pack(C.byref(net), C.c_void_p(blob.data_ptr()), nbytes,
+                                                     C.c_void_p(st.cuda_stream)), "rvo3d_policy_rnn_tiles_pack")
+            st.synchronize()  # (the contiguous copies above die with this scope)
+        out = dict(blob=blob, blob_bytes=nbytes, hidden=r.hidden_dim, in_dim=r.input_dim, state_dim=r.state_dim,
+                   bidir=1 if bi else 0, tanh=isinstance(acts[0][-1], nn.Tanh))
+        self._tiles_blob = (key, out)
+        return out
+
     def prepare_input(self, obs, cnt, plan, cache):
         """The reader's features [rows, Kp] as the A operand of the first MLP layer: rvo3d_reader_first_step for every
         row (one GRU cell step per direction from h = 0, direction sum, concat, LayerNorm: exact for rows with at most

@@ -72,6 +72,44 @@ def synthetic_world(E: int, N: int, map_size, n_points: int = 2, nb: int = 0, se
     return World(wp, np.full((E, N), n_points, np.int32), np.asarray(map_size, dtype=np.float64), bld)
 
 
+def crossing_world(E: int, N: int, map_size, radius: float | None = None, alt_spread: float = 1.0,
+                   angle_jitter: float = 0.05, radius_jitter: float = 0.5, min_sep: float = 1.0,
+                   seed: int = 1234) -> World:
+    """The classical RVO swap scene: per env, N starts on a horizontal ring around the map's centre c (angles evenly
+    spaced with a random rotation per env and +-angle_jitter rad per drone, radius +-radius_jitter, altitude
+    c_z +-alt_spread), each destination antipodal through the centre (2 c - start), rounded to 2 decimals; starts at
+    least min_sep apart (a start that is too close is redrawn).  Every drone flies at the centre: the scene puts
+    drones on collision course by construction (velocity-obstacle rows in the observations).  radius: default
+    0.4 min(L, W).  rng = Philox(seed, stream e) per env, as synthetic_world."""
+    L, Wd, H = (float(x) for x in map_size)
+    c = np.array([L / 2, Wd / 2, H / 2])
+    R = 0.4 * min(L, Wd) if radius is None else float(radius)
+    if R + radius_jitter > min(L, Wd) / 2 - 1.0 or alt_spread > H / 2 - 1.0:
+        raise ValueError("the ring does not fit inside the map (1 m margin)")
+    wp = np.empty((E, N, 2, 3))
+
+    def draw(rng, i, rot):
+        a = rot + 2 * np.pi * i / N + rng.uniform(-angle_jitter, angle_jitter)
+        rr = R + rng.uniform(-radius_jitter, radius_jitter)
+        return np.round(c + np.array([rr * np.cos(a), rr * np.sin(a), rng.uniform(-alt_spread, alt_spread)]), 2)
+
+    for e in range(E):
+        rng = np.random.Generator(np.random.Philox(key=seed, counter=[0, 0, 0, e]))
+        rot = rng.uniform(0, 2 * np.pi)
+        starts = np.empty((N, 3))
+        for i in range(N):
+            starts[i] = draw(rng, i, rot)
+            tries = 0
+            while i and tries < 200 and np.min(np.linalg.norm(starts[:i] - starts[i], axis=1)) < min_sep:
+                starts[i] = draw(rng, i, rot)
+                tries += 1
+            if i and np.min(np.linalg.norm(starts[:i] - starts[i], axis=1)) < min_sep:
+                raise ValueError(f"cannot place {N} starts {min_sep} m apart on a ring of radius {R}")
+        wp[e, :, 0] = starts
+        wp[e, :, 1] = np.round(2 * c - starts, 2)
+    return World(wp, np.full((E, N), 2, np.int32), np.asarray(map_size, dtype=np.float64), np.zeros((0, 4)))
+
+
 def synthetic_actions(E: int, N: int, step: int, seed: int = 1234) -> np.ndarray:
     """round(U(-1,1)^3 * [1, 0.3, 0.15], 2) from Philox(seed, step)."""
     rng = np.random.Generator(np.random.Philox(key=seed + 7, counter=[0, 0, 0, step]))

@@ -268,6 +268,32 @@ int rvo3d_policy_rows(const rvo3d_rnn_policy *net, const float *obs, int64_t obs
                       const int32_t *list, int32_t *count, int32_t *done_blocks, int32_t tanh_out, const float *log_std,
                       float std_factor, uint64_t seed, uint64_t step, float *act, float *logp, float *val, void *stream);
 
+/* The same policy step as rvo3d_policy_rows for the listed rows, built for DENSE lists (worlds where many drones are on a
+ * collision course): the rows go in 32-row tiles through the matrix cores (v_mfma_f32_32x32x16_bf16; bf16 operands,
+ * float32 accumulation, float32 gate math, LayerNorm and hidden state).  The (bi)GRU runs per row over its vo_count VO
+ * rows (forward 0..k-1, reverse k-1..0, as pack_padded_sequence does; directions summed), then concat + LayerNorm, both
+ * state_dim + hidden -> 256 -> 256 -> 3 / 1 stacks (ReLU; tanh on mu when tanh_out), and the tail of rvo3d_policy_rows
+ * (Philox4x32-10 noise with counter (row, step), log-probability, np.round(a, 2), the stores act / logp / val; dbg_mu
+ * [rows][3], nullable, receives mu) - for the listed rows only.  The list (list, count) is sorted on the device into
+ * per-count sub-lists in `work` (rvo3d_policy_rnn_tiles_work_bytes(max_rows, slots) bytes, zero before the first call and
+ * left zero by every call), so a tile's recurrence is as long as its rows'; the last workgroup out zeroes count and
+ * done_blocks [1] (zero before the first call) as rvo3d_policy_rows does.  No host synchronisation; the launch grid does
+ * not depend on the count.  `step` is taken by value: this call ignores rvo3d_rollout_set_step_counter's counter.
+ * max_rows: the rows of obs / vo_count / act / logp / val / dbg_mu (list entries outside 0..max_rows-1 are skipped).
+ * Shapes: hidden 64 or 256, in_dim 9, state_dim 1..16, slots 1..12, GRU or biGRU (bidir), heads (256, 256).
+ * rvo3d_policy_rnn_tiles_pack lays out the weights of `net` (float32 as the modules store them, slots ignored) in a
+ * device blob of rvo3d_policy_rnn_tiles_blob_bytes(hidden, in_dim, state_dim, bidir) bytes (16-byte aligned; -1 for a
+ * shape without an instantiation); repack after every optimizer step.  The call checks blob_bytes against the shape it is
+ * given, and the kernel the shape the blob records: a blob packed for another shape computes nothing. */
+int64_t rvo3d_policy_rnn_tiles_blob_bytes(int32_t hidden, int32_t in_dim, int32_t state_dim, int32_t bidir);
+int rvo3d_policy_rnn_tiles_pack(const rvo3d_rnn_policy *net, void *blob, int64_t blob_bytes, void *stream);
+int64_t rvo3d_policy_rnn_tiles_work_bytes(int64_t max_rows, int32_t slots);
+int rvo3d_policy_rnn_tiles(const void *blob, int64_t blob_bytes, int32_t hidden, int32_t in_dim, int32_t state_dim,
+                           int32_t bidir, const float *obs, int64_t obs_ld, const int32_t *vo_count, const int32_t *list,
+                           int32_t *count, int32_t *done_blocks, int32_t *work, int64_t max_rows, int32_t slots,
+                           int32_t tanh_out, const float *log_std, float std_factor, uint64_t seed, uint64_t step,
+                           float *act, float *logp, float *val, float *dbg_mu, void *stream);
+
 /* Replaying a rollout step as a HIP graph.  The three (MLP policy) or five (biGRU policy) launches of a rollout step take
  * every argument by value, the noise counter `step` included: a captured graph would draw the same noise on every
  * replay.  With a device counter registered here (uint64 in device memory, or NULL to unregister; process-wide), every
