@@ -4,6 +4,7 @@
 #include "../../include/rvo3d.h"
 #include "rvo3d_device.hpp"
 
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -219,50 +220,34 @@ bool allow_lds_all(int bytes) {
 #define RVO3D_MLP_WAVES 8
 #endif
 namespace {
-constexpr int kMlpWaves = RVO3D_MLP_WAVES;  // waves per workgroup of policy_mlp_kernel
-template <int KS1>
-int launch_policy_mlp(const rvo3d::PolicyMlpArgs& A, unsigned grid, hipStream_t s) {
-  constexpr int lds = rvo3d::mlp_lds_bytes(KS1);
-  // more than 64 KB of dynamic LDS needs the attribute, once per device (the function object is per device) and
-  // instantiation; a lost race between two threads sets it twice, which is harmless
+constexpr int kMlpWaves = RVO3D_MLP_WAVES;  // waves per workgroup of policy_mlp_kernel / policy_mlp_x3_kernel
+// More than 64 KB of dynamic LDS needs the attribute, once per device (the function object is per device) and
+// instantiation; a lost race between two threads sets it twice, which is harmless
+template <auto Kernel>
+int allow_dynamic_lds(int bytes) {
   static uint64_t attr_set = 0;
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64 || !((attr_set >> dev) & 1)) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rvo3d::policy_mlp_kernel<KS1, kMlpWaves>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     if (dev >= 0 && dev < 64) attr_set |= (uint64_t)1 << dev;
   }
-  hipLaunchKernelGGL((rvo3d::policy_mlp_kernel<KS1, kMlpWaves>), dim3(grid), dim3(64 * kMlpWaves), lds, s, A);
-  HIP_TRY(hipGetLastError());
   return RVO3D_OK;
 }
-template <int KS1>
-int launch_policy_mlp_x3(const rvo3d::PolicyMlpArgs& A, unsigned grid, hipStream_t s) {
-  constexpr int lds = rvo3d::kX3LdsBytes;
-  static uint64_t attr_set = 0;  // (as launch_policy_mlp)
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !((attr_set >> dev) & 1)) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rvo3d::policy_mlp_x3_kernel<KS1, kMlpWaves>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (dev >= 0 && dev < 64) attr_set |= (uint64_t)1 << dev;
-  }
-  hipLaunchKernelGGL((rvo3d::policy_mlp_x3_kernel<KS1, kMlpWaves>), dim3(grid), dim3(64 * kMlpWaves), lds, s, A);
+// X3: the split-bf16 (float32-class) kernel of csrc/rvo3d_policy_mlp_x3.hpp, else the bf16 one
+template <bool X3, int KS1>
+int launch_policy_mlp(const rvo3d::PolicyMlpArgs& A, unsigned grid, hipStream_t s) {
+  constexpr auto kernel = X3 ? rvo3d::policy_mlp_x3_kernel<KS1, kMlpWaves> : rvo3d::policy_mlp_kernel<KS1, kMlpWaves>;
+  constexpr int lds = X3 ? rvo3d::kX3LdsBytes : rvo3d::mlp_lds_bytes(KS1);
+  if (int rc = allow_dynamic_lds<kernel>(lds)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kMlpWaves), lds, s, A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
 }
 template <int H, int ND>
 int launch_policy_rnn_tiles(const rvo3d::RnnTilesArgs& A, unsigned grid, hipStream_t s) {
   constexpr int lds = rvo3d::kRnnTilesWaves * H * 128;  // the running hidden state, 128 H bytes per wave
-  static uint64_t attr_set = 0;  // (as launch_policy_mlp)
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !((attr_set >> dev) & 1)) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rvo3d::policy_rnn_tiles_kernel<H, ND>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (dev >= 0 && dev < 64) attr_set |= (uint64_t)1 << dev;
-  }
+  if (int rc = allow_dynamic_lds<rvo3d::policy_rnn_tiles_kernel<H, ND>>(lds)) return rc;
   hipLaunchKernelGGL((rvo3d::policy_rnn_tiles_kernel<H, ND>), dim3(grid), dim3(64 * rvo3d::kRnnTilesWaves), lds, s, A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
@@ -270,12 +255,116 @@ int launch_policy_rnn_tiles(const rvo3d::RnnTilesArgs& A, unsigned grid, hipStre
 bool rnn_tiles_shape_ok(int32_t hidden, int32_t in_dim, int32_t state_dim) {
   return (hidden == 64 || hidden == 256) && in_dim == 9 && state_dim >= 1 && state_dim <= 16;
 }
-}  // namespace
 
 // optional noise counter in device memory (rvo3d_rollout_set_step_counter): added to the `step` of every sampling launch,
 // advanced by rvo3d_rollout_account - lets a caller replay a captured launch sequence (a HIP graph) with fresh noise
-#include <atomic>
-namespace { std::atomic<uint64_t*> g_step_dev{nullptr}; }
+std::atomic<uint64_t*> g_step_dev{nullptr};
+
+// The sampling tail's arguments as every policy-step entry point takes them, with the registered noise counter
+rvo3d::PolicySampleArgs sample_args(int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed, uint64_t step,
+                                    int64_t rows, float* act, float* logp, float* val, float* dbg_mu, float* dbg_raw) {
+  rvo3d::PolicySampleArgs S{};
+  S.tanh_out = tanh_out; S.log_std = log_std; S.std_factor = std_factor; S.seed = seed; S.step = step;
+  S.step_dev = g_step_dev.load();
+  S.rows = rows; S.act = act; S.logp = logp; S.val = val; S.dbg_mu = dbg_mu; S.dbg_raw = dbg_raw;
+  return S;
+}
+
+// The weights of an rvo3d_rnn_policy into a launch's arguments, in two parts so that each caller keeps the order of its
+// checks: the reader (forward direction and LayerNorm required, the reverse direction all or nothing), then the actor's
+// and the critic's stacks ([0] / [1]; also the weights of the mlp packs).
+template <class Args>
+int copy_reader(Args& A, const rvo3d_rnn_policy& net) {
+  if (!net.w_ih_f || !net.w_hh_f || !net.b_ih_f || !net.b_hh_f || !net.ln_w || !net.ln_b)
+    return fail(RVO3D_ERR_INVALID, "null reader weight");
+  const bool bi = net.w_ih_r != nullptr;
+  if (bi != (net.w_hh_r != nullptr) || bi != (net.b_ih_r != nullptr) || bi != (net.b_hh_r != nullptr))
+    return fail(RVO3D_ERR_INVALID, "the reverse direction needs all four of w_ih_r / w_hh_r / b_ih_r / b_hh_r");
+  A.w_ih[0] = net.w_ih_f; A.w_hh[0] = net.w_hh_f; A.b_ih[0] = net.b_ih_f; A.b_hh[0] = net.b_hh_f;
+  A.w_ih[1] = net.w_ih_r; A.w_hh[1] = net.w_hh_r; A.b_ih[1] = net.b_ih_r; A.b_hh[1] = net.b_hh_r;
+  A.ln_w = net.ln_w; A.ln_b = net.ln_b; A.eps = net.ln_eps;
+  return RVO3D_OK;
+}
+template <class Args>
+int copy_heads(Args& A, const rvo3d_mlp_weights& pi, const rvo3d_mlp_weights& v, const char* missing) {
+  const rvo3d_mlp_weights* n[2] = {&pi, &v};
+  for (int i = 0; i < 2; ++i) {
+    if (!n[i]->w1 || !n[i]->b1 || !n[i]->w2 || !n[i]->b2 || !n[i]->w3 || !n[i]->b3)
+      return fail(RVO3D_ERR_INVALID, missing);
+    A.w1[i] = n[i]->w1; A.b1[i] = n[i]->b1; A.w2[i] = n[i]->w2; A.b2[i] = n[i]->b2; A.w3[i] = n[i]->w3; A.b3[i] = n[i]->b3;
+  }
+  return RVO3D_OK;
+}
+
+// rvo3d_policy_mlp_* (X3 = false) and rvo3d_policy_mlp_x3_* (X3 = true): the same arguments, checks and launch geometry;
+// the precision picks the kernels and the blob layout.  (Called between the entry points' RVO3D_API_BEGIN / END.)
+template <bool X3>
+int64_t mlp_net_bytes(int ks1) { return X3 ? rvo3d::mlp_x3_net_bytes(ks1) : rvo3d::mlp_net_bytes(ks1); }
+
+template <bool X3>
+int64_t policy_mlp_blob_bytes(int32_t obs_width) {
+  if (obs_width < 1 || obs_width > 126) return -1;
+  return 2 * mlp_net_bytes<X3>(rvo3d::mlp_ks1(obs_width));
+}
+
+template <bool X3>
+int policy_mlp_pack(const rvo3d_mlp_weights* pi, const rvo3d_mlp_weights* v, int32_t obs_width, void* blob, void* stream) {
+  if (!pi || !v || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  rvo3d::MlpPackArgs A;
+  A.k_in = obs_width; A.ks1 = rvo3d::mlp_ks1(obs_width);
+  if (int rc = copy_heads(A, *pi, *v, "null weight pointer")) return rc;
+  A.blob = static_cast<unsigned char*>(blob);
+  hipLaunchKernelGGL(X3 ? rvo3d::mlp_x3_pack_kernel : rvo3d::mlp_pack_kernel, dim3(64, 2), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+}
+
+template <bool X3>
+int policy_mlp_sample(const void* blob, int32_t obs_width, const float* obs, int64_t obs_ld, int64_t rows,
+                      const int32_t* vo_count, int32_t state_dim, int32_t row_dim, int32_t tanh_out, const float* log_std,
+                      float std_factor, uint64_t seed, uint64_t step, float* act, float* logp, float* val, float* dbg_mu,
+                      float* dbg_raw, void* stream) {
+  if (!blob || !obs || !log_std || !act || !logp || !val) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
+  if (rows < 0 || obs_ld < obs_width) return fail(RVO3D_ERR_INVALID, "rows < 0 or obs_ld < obs_width");
+  if (rows > 0 && ((rows - 1) * obs_ld + obs_width) * 4 > (int64_t)0x7fffffff)
+    return fail(RVO3D_ERR_INVALID, "the observation array must stay below 2 GiB per call (32-bit buffer offsets): split the rows");
+  if (reinterpret_cast<uintptr_t>(obs) & 3) return fail(RVO3D_ERR_INVALID, "obs must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  if (rows == 0) return RVO3D_OK;
+  int dev = 0, cus = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const int ks1 = rvo3d::mlp_ks1(obs_width);
+  rvo3d::PolicyMlpArgs A;
+  A.blob = static_cast<const unsigned char*>(blob); A.net_bytes = mlp_net_bytes<X3>(ks1);
+  A.obs = obs; A.ld_obs = obs_ld; A.k_in = obs_width;
+  A.cnt = vo_count; A.state_dim = state_dim; A.row_dim = row_dim;
+  if (vo_count && (state_dim < 0 || row_dim < 1 || state_dim > obs_width))
+    return fail(RVO3D_ERR_INVALID, "vo_count needs 0 <= state_dim <= obs_width and row_dim >= 1");
+  A.S = sample_args(tanh_out, log_std, std_factor, seed, step, rows, act, logp, val, dbg_mu, dbg_raw);
+  // one workgroup per CU, half of them per network; every wave takes 64 rows per trip
+  const int64_t nchunks = (rows + 63) / 64;
+  int64_t G = (nchunks + kMlpWaves - 1) / kMlpWaves;
+  const int64_t Gmax = cus >= 2 ? cus / 2 : 1;
+  if (G > Gmax) G = Gmax;
+  const unsigned grid = (unsigned)(2 * G);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (ks1) {
+    case 1: return launch_policy_mlp<X3, 1>(A, grid, s);
+    case 2: return launch_policy_mlp<X3, 2>(A, grid, s);
+    case 3: return launch_policy_mlp<X3, 3>(A, grid, s);
+    case 4: return launch_policy_mlp<X3, 4>(A, grid, s);
+    case 5: return launch_policy_mlp<X3, 5>(A, grid, s);
+    case 6: return launch_policy_mlp<X3, 6>(A, grid, s);
+    case 7: return launch_policy_mlp<X3, 7>(A, grid, s);
+    default: return launch_policy_mlp<X3, 8>(A, grid, s);
+  }
+}
+}  // namespace
 
 extern "C" {
 
@@ -693,13 +782,10 @@ int rvo3d_policy_sample(const rvo3d_policy_heads* hd, int64_t rows, float std_fa
     return fail(RVO3D_ERR_INVALID, "null pointer");
   if (rows < 0) return fail(RVO3D_ERR_INVALID, "rows < 0");
   if (rows == 0) return RVO3D_OK;
-  rvo3d::PolicySampleArgs A;
-  A.h_pi = hd->h_pi; A.h_v = hd->h_v; A.ld_pi = hd->ld_pi; A.ld_v = hd->ld_v;
-  A.hidden = hd->hidden; A.tanh_out = hd->hidden == 0 ? 0 : hd->tanh_out;  // (mu given: already activated)
-  A.w_pi = hd->w_pi; A.b_pi = hd->b_pi; A.w_v = hd->w_v; A.b_v = hd->b_v; A.log_std = hd->log_std;
-  A.std_factor = std_factor; A.seed = seed; A.step = step; A.rows = rows;
-  A.step_dev = g_step_dev.load();
-  A.act = act; A.logp = logp; A.val = val; A.dbg_mu = dbg_mu; A.dbg_raw = dbg_raw;
+  rvo3d::PolicySampleArgs A = sample_args(hd->hidden == 0 ? 0 : hd->tanh_out,  // (mu given: already activated)
+                                          hd->log_std, std_factor, seed, step, rows, act, logp, val, dbg_mu, dbg_raw);
+  A.h_pi = hd->h_pi; A.h_v = hd->h_v; A.ld_pi = hd->ld_pi; A.ld_v = hd->ld_v; A.hidden = hd->hidden;
+  A.w_pi = hd->w_pi; A.b_pi = hd->b_pi; A.w_v = hd->w_v; A.b_v = hd->b_v;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hd->hidden == 0) {
     if (hd->ld_pi < 3 || hd->ld_v < 1) return fail(RVO3D_ERR_INVALID, "hidden == 0 needs ld_pi >= 3 and ld_v >= 1");
@@ -730,29 +816,12 @@ int rvo3d_policy_sample(const rvo3d_policy_heads* hd, int64_t rows, float std_fa
   RVO3D_API_END
 }
 
-int64_t rvo3d_policy_mlp_blob_bytes(int32_t obs_width) {
-  if (obs_width < 1 || obs_width > 126) return -1;
-  return 2 * rvo3d::mlp_net_bytes(rvo3d::mlp_ks1(obs_width));
-}
+int64_t rvo3d_policy_mlp_blob_bytes(int32_t obs_width) { return policy_mlp_blob_bytes<false>(obs_width); }
 
 int rvo3d_policy_mlp_pack(const rvo3d_mlp_weights* pi, const rvo3d_mlp_weights* v, int32_t obs_width, void* blob,
                           void* stream) {
   RVO3D_API_BEGIN
-  if (!pi || !v || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
-  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
-  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
-  const rvo3d_mlp_weights* n[2] = {pi, v};
-  rvo3d::MlpPackArgs A;
-  A.k_in = obs_width; A.ks1 = rvo3d::mlp_ks1(obs_width);
-  for (int i = 0; i < 2; ++i) {
-    if (!n[i]->w1 || !n[i]->b1 || !n[i]->w2 || !n[i]->b2 || !n[i]->w3 || !n[i]->b3)
-      return fail(RVO3D_ERR_INVALID, "null weight pointer");
-    A.w1[i] = n[i]->w1; A.b1[i] = n[i]->b1; A.w2[i] = n[i]->w2; A.b2[i] = n[i]->b2; A.w3[i] = n[i]->w3; A.b3[i] = n[i]->b3;
-  }
-  A.blob = static_cast<unsigned char*>(blob);
-  hipLaunchKernelGGL(rvo3d::mlp_pack_kernel, dim3(64, 2), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-  HIP_TRY(hipGetLastError());
-  return RVO3D_OK;
+  return policy_mlp_pack<false>(pi, v, obs_width, blob, stream);
   RVO3D_API_END
 }
 
@@ -760,45 +829,8 @@ int rvo3d_policy_mlp_sample(const void* blob, int32_t obs_width, const float* ob
                             const int32_t* vo_count, int32_t state_dim, int32_t row_dim, int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed, uint64_t step,
                             float* act, float* logp, float* val, float* dbg_mu, float* dbg_raw, void* stream) {
   RVO3D_API_BEGIN
-  if (!blob || !obs || !log_std || !act || !logp || !val) return fail(RVO3D_ERR_INVALID, "null pointer");
-  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
-  if (rows < 0 || obs_ld < obs_width) return fail(RVO3D_ERR_INVALID, "rows < 0 or obs_ld < obs_width");
-  if (rows > 0 && ((rows - 1) * obs_ld + obs_width) * 4 > (int64_t)0x7fffffff)
-    return fail(RVO3D_ERR_INVALID, "the observation array must stay below 2 GiB per call (32-bit buffer offsets): split the rows");
-  if (reinterpret_cast<uintptr_t>(obs) & 3) return fail(RVO3D_ERR_INVALID, "obs must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
-  if (rows == 0) return RVO3D_OK;
-  int dev = 0, cus = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int ks1 = rvo3d::mlp_ks1(obs_width);
-  rvo3d::PolicyMlpArgs A;
-  A.blob = static_cast<const unsigned char*>(blob); A.net_bytes = rvo3d::mlp_net_bytes(ks1);
-  A.obs = obs; A.ld_obs = obs_ld; A.k_in = obs_width;
-  A.cnt = vo_count; A.state_dim = state_dim; A.row_dim = row_dim;
-  if (vo_count && (state_dim < 0 || row_dim < 1 || state_dim > obs_width))
-    return fail(RVO3D_ERR_INVALID, "vo_count needs 0 <= state_dim <= obs_width and row_dim >= 1");
-  A.S = rvo3d::PolicySampleArgs{};
-  A.S.tanh_out = tanh_out; A.S.log_std = log_std; A.S.std_factor = std_factor; A.S.seed = seed; A.S.step = step;
-  A.S.step_dev = g_step_dev.load();
-  A.S.rows = rows; A.S.act = act; A.S.logp = logp; A.S.val = val; A.S.dbg_mu = dbg_mu; A.S.dbg_raw = dbg_raw;
-  // one workgroup per CU, half of them per network; every wave takes 64 rows per trip
-  const int64_t nchunks = (rows + 63) / 64;
-  int64_t G = (nchunks + kMlpWaves - 1) / kMlpWaves;
-  const int64_t Gmax = cus >= 2 ? cus / 2 : 1;
-  if (G > Gmax) G = Gmax;
-  const unsigned grid = (unsigned)(2 * G);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (ks1) {
-    case 1: return launch_policy_mlp<1>(A, grid, s);
-    case 2: return launch_policy_mlp<2>(A, grid, s);
-    case 3: return launch_policy_mlp<3>(A, grid, s);
-    case 4: return launch_policy_mlp<4>(A, grid, s);
-    case 5: return launch_policy_mlp<5>(A, grid, s);
-    case 6: return launch_policy_mlp<6>(A, grid, s);
-    case 7: return launch_policy_mlp<7>(A, grid, s);
-    default: return launch_policy_mlp<8>(A, grid, s);
-  }
+  return policy_mlp_sample<false>(blob, obs_width, obs, obs_ld, rows, vo_count, state_dim, row_dim, tanh_out, log_std,
+                                  std_factor, seed, step, act, logp, val, dbg_mu, dbg_raw, stream);
   RVO3D_API_END
 }
 
@@ -807,29 +839,12 @@ int rvo3d_policy_mlp_sample(const void* blob, int32_t obs_width, const float* ob
 // float32 accumulation; the first layer's bias as hi and lo against an exact 1, b2 and the head biases in float32, ReLU
 // on the float32 sums before the split; the per-row tail, the noise, vo_count and the range-checked observation reads
 // are those of rvo3d_policy_mlp_sample.  Same arguments and checks.
-int64_t rvo3d_policy_mlp_x3_blob_bytes(int32_t obs_width) {
-  if (obs_width < 1 || obs_width > 126) return -1;
-  return 2 * rvo3d::mlp_x3_net_bytes(rvo3d::mlp_ks1(obs_width));
-}
+int64_t rvo3d_policy_mlp_x3_blob_bytes(int32_t obs_width) { return policy_mlp_blob_bytes<true>(obs_width); }
 
 int rvo3d_policy_mlp_x3_pack(const rvo3d_mlp_weights* pi, const rvo3d_mlp_weights* v, int32_t obs_width, void* blob,
                              void* stream) {
   RVO3D_API_BEGIN
-  if (!pi || !v || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
-  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
-  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
-  const rvo3d_mlp_weights* n[2] = {pi, v};
-  rvo3d::MlpPackArgs A;
-  A.k_in = obs_width; A.ks1 = rvo3d::mlp_ks1(obs_width);
-  for (int i = 0; i < 2; ++i) {
-    if (!n[i]->w1 || !n[i]->b1 || !n[i]->w2 || !n[i]->b2 || !n[i]->w3 || !n[i]->b3)
-      return fail(RVO3D_ERR_INVALID, "null weight pointer");
-    A.w1[i] = n[i]->w1; A.b1[i] = n[i]->b1; A.w2[i] = n[i]->w2; A.b2[i] = n[i]->b2; A.w3[i] = n[i]->w3; A.b3[i] = n[i]->b3;
-  }
-  A.blob = static_cast<unsigned char*>(blob);
-  hipLaunchKernelGGL(rvo3d::mlp_x3_pack_kernel, dim3(64, 2), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-  HIP_TRY(hipGetLastError());
-  return RVO3D_OK;
+  return policy_mlp_pack<true>(pi, v, obs_width, blob, stream);
   RVO3D_API_END
 }
 
@@ -837,45 +852,8 @@ int rvo3d_policy_mlp_x3_sample(const void* blob, int32_t obs_width, const float*
                                const int32_t* vo_count, int32_t state_dim, int32_t row_dim, int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed, uint64_t step,
                                float* act, float* logp, float* val, float* dbg_mu, float* dbg_raw, void* stream) {
   RVO3D_API_BEGIN
-  if (!blob || !obs || !log_std || !act || !logp || !val) return fail(RVO3D_ERR_INVALID, "null pointer");
-  if (obs_width < 1 || obs_width > 126) return fail(RVO3D_ERR_INVALID, "obs_width must be 1..126");
-  if (rows < 0 || obs_ld < obs_width) return fail(RVO3D_ERR_INVALID, "rows < 0 or obs_ld < obs_width");
-  if (rows > 0 && ((rows - 1) * obs_ld + obs_width) * 4 > (int64_t)0x7fffffff)
-    return fail(RVO3D_ERR_INVALID, "the observation array must stay below 2 GiB per call (32-bit buffer offsets): split the rows");
-  if (reinterpret_cast<uintptr_t>(obs) & 3) return fail(RVO3D_ERR_INVALID, "obs must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
-  if (rows == 0) return RVO3D_OK;
-  int dev = 0, cus = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int ks1 = rvo3d::mlp_ks1(obs_width);
-  rvo3d::PolicyMlpArgs A;
-  A.blob = static_cast<const unsigned char*>(blob); A.net_bytes = rvo3d::mlp_x3_net_bytes(ks1);
-  A.obs = obs; A.ld_obs = obs_ld; A.k_in = obs_width;
-  A.cnt = vo_count; A.state_dim = state_dim; A.row_dim = row_dim;
-  if (vo_count && (state_dim < 0 || row_dim < 1 || state_dim > obs_width))
-    return fail(RVO3D_ERR_INVALID, "vo_count needs 0 <= state_dim <= obs_width and row_dim >= 1");
-  A.S = rvo3d::PolicySampleArgs{};
-  A.S.tanh_out = tanh_out; A.S.log_std = log_std; A.S.std_factor = std_factor; A.S.seed = seed; A.S.step = step;
-  A.S.step_dev = g_step_dev.load();
-  A.S.rows = rows; A.S.act = act; A.S.logp = logp; A.S.val = val; A.S.dbg_mu = dbg_mu; A.S.dbg_raw = dbg_raw;
-  // one workgroup per CU, half of them per network; every wave takes 64 rows per trip (as rvo3d_policy_mlp_sample)
-  const int64_t nchunks = (rows + 63) / 64;
-  int64_t G = (nchunks + kMlpWaves - 1) / kMlpWaves;
-  const int64_t Gmax = cus >= 2 ? cus / 2 : 1;
-  if (G > Gmax) G = Gmax;
-  const unsigned grid = (unsigned)(2 * G);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (ks1) {
-    case 1: return launch_policy_mlp_x3<1>(A, grid, s);
-    case 2: return launch_policy_mlp_x3<2>(A, grid, s);
-    case 3: return launch_policy_mlp_x3<3>(A, grid, s);
-    case 4: return launch_policy_mlp_x3<4>(A, grid, s);
-    case 5: return launch_policy_mlp_x3<5>(A, grid, s);
-    case 6: return launch_policy_mlp_x3<6>(A, grid, s);
-    case 7: return launch_policy_mlp_x3<7>(A, grid, s);
-    default: return launch_policy_mlp_x3<8>(A, grid, s);
-  }
+  return policy_mlp_sample<true>(blob, obs_width, obs, obs_ld, rows, vo_count, state_dim, row_dim, tanh_out, log_std,
+                                 std_factor, seed, step, act, logp, val, dbg_mu, dbg_raw, stream);
   RVO3D_API_END
 }
 
@@ -908,31 +886,16 @@ int rvo3d_policy_rows(const rvo3d_rnn_policy* net, const float* obs, int64_t obs
   RVO3D_API_BEGIN
   if (!net || !obs || !vo_count || !list || !count || !done_blocks || !log_std || !act || !logp || !val)
     return fail(RVO3D_ERR_INVALID, "null pointer");
-  if (!net->w_ih_f || !net->w_hh_f || !net->b_ih_f || !net->b_hh_f || !net->ln_w || !net->ln_b)
-    return fail(RVO3D_ERR_INVALID, "null reader weight");
-  const bool bi = net->w_ih_r != nullptr;
-  if (bi != (net->w_hh_r != nullptr) || bi != (net->b_ih_r != nullptr) || bi != (net->b_hh_r != nullptr))
-    return fail(RVO3D_ERR_INVALID, "the reverse direction needs all four of w_ih_r / w_hh_r / b_ih_r / b_hh_r");
+  rvo3d::PolicyRowsArgs A;
+  if (int rc = copy_reader(A, *net)) return rc;
   if (net->hidden < 1 || net->hidden > 256 || net->in_dim < 1 || net->in_dim > rvo3d::kReaderMaxIn || net->state_dim < 1 ||
       net->state_dim > rvo3d::kReaderMaxSd || net->slots < 1 || net->slots > 16)
     return fail(RVO3D_ERR_INVALID, "hidden <= 256, in_dim <= 16, state_dim <= 32, slots <= 16");
   if (obs_ld < net->state_dim + net->slots * net->in_dim) return fail(RVO3D_ERR_INVALID, "obs_ld too small");
-  const rvo3d_mlp_weights* m[2] = {&net->pi, &net->v};
-  rvo3d::PolicyRowsArgs A;
+  if (int rc = copy_heads(A, net->pi, net->v, "null head weight")) return rc;
   A.obs = obs; A.obs_ld = obs_ld; A.cnt = vo_count; A.list = list; A.count = count; A.done_blocks = done_blocks;
   A.state_dim = net->state_dim; A.in_dim = net->in_dim; A.H = net->hidden; A.slots = net->slots;
-  A.w_ih[0] = net->w_ih_f; A.w_hh[0] = net->w_hh_f; A.b_ih[0] = net->b_ih_f; A.b_hh[0] = net->b_hh_f;
-  A.w_ih[1] = net->w_ih_r; A.w_hh[1] = net->w_hh_r; A.b_ih[1] = net->b_ih_r; A.b_hh[1] = net->b_hh_r;
-  A.ln_w = net->ln_w; A.ln_b = net->ln_b; A.eps = net->ln_eps;
-  for (int i = 0; i < 2; ++i) {
-    if (!m[i]->w1 || !m[i]->b1 || !m[i]->w2 || !m[i]->b2 || !m[i]->w3 || !m[i]->b3)
-      return fail(RVO3D_ERR_INVALID, "null head weight");
-    A.w1[i] = m[i]->w1; A.b1[i] = m[i]->b1; A.w2[i] = m[i]->w2; A.b2[i] = m[i]->b2; A.w3[i] = m[i]->w3; A.b3[i] = m[i]->b3;
-  }
-  A.S = rvo3d::PolicySampleArgs{};
-  A.S.tanh_out = tanh_out; A.S.log_std = log_std; A.S.std_factor = std_factor; A.S.seed = seed; A.S.step = step;
-  A.S.step_dev = g_step_dev.load();
-  A.S.act = act; A.S.logp = logp; A.S.val = val;
+  A.S = sample_args(tanh_out, log_std, std_factor, seed, step, 0, act, logp, val, nullptr, nullptr);
   hipLaunchKernelGGL(rvo3d::policy_rows_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
@@ -954,27 +917,16 @@ int64_t rvo3d_policy_rnn_tiles_work_bytes(int64_t max_rows, int32_t slots) {
 int rvo3d_policy_rnn_tiles_pack(const rvo3d_rnn_policy* net, void* blob, int64_t blob_bytes, void* stream) {
   RVO3D_API_BEGIN
   if (!net || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
-  if (!net->w_ih_f || !net->w_hh_f || !net->b_ih_f || !net->b_hh_f || !net->ln_w || !net->ln_b)
-    return fail(RVO3D_ERR_INVALID, "null reader weight");
+  rvo3d::RnnTilesPackArgs A;
+  if (int rc = copy_reader(A, *net)) return rc;
   const bool bi = net->w_ih_r != nullptr;
-  if (bi != (net->w_hh_r != nullptr) || bi != (net->b_ih_r != nullptr) || bi != (net->b_hh_r != nullptr))
-    return fail(RVO3D_ERR_INVALID, "the reverse direction needs all four of w_ih_r / w_hh_r / b_ih_r / b_hh_r");
   if (!rnn_tiles_shape_ok(net->hidden, net->in_dim, net->state_dim))
     return fail(RVO3D_ERR_INVALID, "rnn tiles: hidden must be 64 or 256, in_dim 9, state_dim 1..16");
   if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
   if (blob_bytes != rvo3d_policy_rnn_tiles_blob_bytes(net->hidden, net->in_dim, net->state_dim, bi))
     return fail(RVO3D_ERR_INVALID, "blob_bytes does not match rvo3d_policy_rnn_tiles_blob_bytes for this shape");
-  const rvo3d_mlp_weights* m[2] = {&net->pi, &net->v};
-  rvo3d::RnnTilesPackArgs A;
-  A.H = net->hidden; A.ND = bi ? 2 : 1; A.SD = net->state_dim; A.IN = net->in_dim; A.eps = net->ln_eps;
-  A.w_ih[0] = net->w_ih_f; A.w_hh[0] = net->w_hh_f; A.b_ih[0] = net->b_ih_f; A.b_hh[0] = net->b_hh_f;
-  A.w_ih[1] = net->w_ih_r; A.w_hh[1] = net->w_hh_r; A.b_ih[1] = net->b_ih_r; A.b_hh[1] = net->b_hh_r;
-  A.ln_w = net->ln_w; A.ln_b = net->ln_b;
-  for (int i = 0; i < 2; ++i) {
-    if (!m[i]->w1 || !m[i]->b1 || !m[i]->w2 || !m[i]->b2 || !m[i]->w3 || !m[i]->b3)
-      return fail(RVO3D_ERR_INVALID, "null head weight");
-    A.w1[i] = m[i]->w1; A.b1[i] = m[i]->b1; A.w2[i] = m[i]->w2; A.b2[i] = m[i]->b2; A.w3[i] = m[i]->w3; A.b3[i] = m[i]->b3;
-  }
+  if (int rc = copy_heads(A, net->pi, net->v, "null head weight")) return rc;
+  A.H = net->hidden; A.ND = bi ? 2 : 1; A.SD = net->state_dim; A.IN = net->in_dim;
   A.blob = static_cast<unsigned char*>(blob);
   hipLaunchKernelGGL(rvo3d::rnn_tiles_pack_kernel, dim3(128), dim3(256), 0, static_cast<hipStream_t>(stream), A);
   HIP_TRY(hipGetLastError());
@@ -1005,10 +957,8 @@ int rvo3d_policy_rnn_tiles(const void* blob, int64_t blob_bytes, int32_t hidden,
   A.blob = static_cast<const unsigned char*>(blob);
   A.obs = obs; A.obs_ld = obs_ld; A.cnt = vo_count; A.list = list; A.count = count; A.done_blocks = done_blocks;
   A.work = work; A.max_rows = max_rows; A.SD = state_dim; A.slots = slots;
-  A.S = rvo3d::PolicySampleArgs{};
-  A.S.tanh_out = tanh_out; A.S.log_std = log_std; A.S.std_factor = std_factor; A.S.seed = seed; A.S.step = step;
+  A.S = sample_args(tanh_out, log_std, std_factor, seed, step, 0, act, logp, val, dbg_mu, nullptr);
   A.S.step_dev = nullptr;  // (never graph-replayed: the noise counter is `step` alone)
-  A.S.act = act; A.S.logp = logp; A.S.val = val; A.S.dbg_mu = dbg_mu;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(rvo3d::rnn_tiles_bucket_kernel, dim3(256), dim3(256), 0, s, A);
   HIP_TRY(hipGetLastError());

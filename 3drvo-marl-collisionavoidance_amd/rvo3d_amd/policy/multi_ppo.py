@@ -155,7 +155,7 @@ class multi_ppo:
                  save_result=False, counter=0, test_env=None, lr_decay_epoch=1000,
                  max_update_num=None, mpi=False, figure_save_path=None, minibatch_size=None,
                  dist=None, sanitize_rewards=True, amp=False, reference_order=False, fused_rollout=True,
-                 rollout_chunk=None, tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False,
+                 tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False,
                  fused_rnn_tiles=False, **kwargs):
         np.random.seed(seed)
         self.env, self.ac, self.dist = env, ac_policy, dist
@@ -190,7 +190,6 @@ class multi_ppo:
         # opt-in: measured at 64 x 4096, 0.158 ms per step with and 0.157-0.161 without - the gaps between the dependent
         # kernels of a graph are what they are between stream launches
         self.graph_rollout = bool(graph_rollout)
-        self.rollout_chunk = rollout_chunk  # rows per policy pass of the fused rollout (None / 0: all at once)
         # the rollout's policy GEMMs ([E*N, 128] x [128, 512], [E*N, 256] x [256, 256], bf16) through PyTorch's
         # TunableOp: the first call of a shape times hipBLASLt's candidate kernels (<= 3 s per shape) and keeps
         # the fastest - at 64 x 4096 a 256x256x64 stream-K kernel, 70 us, instead of the heuristic's 84 us
@@ -351,10 +350,24 @@ class multi_ppo:
         mb = self.ac.mlp_blob() if mode == "mlp" else self.ac.mlp_blob("x3") if mode == "mlp_x3" else None
         zp = self.ac.zero_vo_plan() if mode in ("rnn0", "rnn_tiles") else None
         tb = self.ac.rnn_tiles_blob() if mode == "rnn_tiles" else None
-        if mode in ("rnn0", "rnn_tiles") and "vo_count" in ac:
-            ac["vo_count"].zero_()  # (the kernels leave it at zero; a rollout that was interrupted half-way may not have)
-        if mode == "rnn_tiles" and "tiles_work" in ac:
-            ac["tiles_work"][:32].zero_()  # (the sub-lists' cursors: likewise)
+        plan = self.ac.fused_plan(dt) if mode == "heads" else None
+        if zp is not None:
+            # the scratch of the rnn modes, kept across rollouts (graph replay needs fixed addresses)
+            slots = env.nm if hasattr(env, "nm") else (env.W - zp["state_dim"]) // 9
+            if mode == "rnn0":
+                zp["rows_net"].slots = slots
+            if "feat0" not in ac or ac["feat0"].shape != (E * N, zp["width"]):
+                ac["feat0"] = torch.empty((E * N, zp["width"]), dtype=torch.float32, device=self.device)
+                ac["vo_list"] = torch.zeros(E * N, dtype=torch.int32, device=self.device)
+                ac["vo_count"] = torch.zeros(2, dtype=torch.int32, device=self.device)   # [count, finished workgroups]
+            else:
+                ac["vo_count"].zero_()  # (the kernels leave it at zero; a rollout that was interrupted half-way may not have)
+        if tb is not None:
+            nw = int(L.rvo3d_policy_rnn_tiles_work_bytes(E * N, slots)) // 4
+            if "tiles_work" not in ac or ac["tiles_work"].numel() != nw:
+                ac["tiles_work"] = torch.zeros(nw, dtype=torch.int32, device=self.device)
+            else:
+                ac["tiles_work"][:32].zero_()  # (the sub-lists' cursors: likewise)
         # Graph replay (graph_rollout=True; the bf16 MLP and biGRU fast paths, "mlp" / "rnn0" only - "mlp_x3" and the
         # others always launch eagerly): the launches of step t - every argument by value,
         # every buffer slot at a fixed address - are captured once per slot into a HIP graph and replayed in later
@@ -362,7 +375,7 @@ class multi_ppo:
         # launches; measured: a graph's kernels keep those gaps - no gain, hence opt-in).  The noise counter then lives in device memory
         # (rvo3d_rollout_set_step_counter: rvo3d_rollout_account advances it).  Only when no episode can time out
         # inside the rollout (that check reads the device) and after one eager rollout (allocations, first calls).
-        use_graph = (self.graph_rollout and mode in ("mlp", "rnn0") and T <= self.max_ep_len and not self.rollout_chunk
+        use_graph = (self.graph_rollout and mode in ("mlp", "rnn0") and T <= self.max_ep_len
                      and getattr(self, "_graph_warm", None) == mode and not getattr(self, "_graph_failed", False))
         self._graph_warm = mode
         if use_graph:
@@ -372,86 +385,67 @@ class multi_ppo:
             _lib.check(L.rvo3d_rollout_set_step_counter(p(self._step_dev)), "rvo3d_rollout_set_step_counter")
         step_arg = lambda: (1 << 32) if (use_graph and not getattr(self, "_graph_failed", False)) else ac["step"]
 
+        # the policy part of a step, one function per mode: observation rows x, their VO counts cnt, the buffer slot's
+        # act / logp / val pointers out
+        def policy_mlp(x, cnt, out):
+            # (the env's counts: column groups that are zero for all rows of a wave are skipped)
+            name = "rvo3d_policy_mlp_sample" if mode == "mlp" else "rvo3d_policy_mlp_x3_sample"
+            _lib.check(getattr(L, name)(p(mb["blob"]), env.W, p(x), x.stride(0), E * N, p(cnt), 12, 9,
+                                        1 if mb["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(), *out,
+                                        None, None, stream()), name)
+
+        def policy_rnn0(x, cnt, out):
+            # rows without a velocity-obstacle row: collapsed first layer (rvo3d_reader_zero_features builds its 20
+            # inputs and lists the rows that do have VO rows) + the MFMA kernel; the listed rows: one workgroup each
+            # ("rnn0", as the modules compute them) or 32-row MFMA tiles grouped by their VO count on the device
+            # ("rnn_tiles"); no host synchronisation
+            f0, vo_count = ac["feat0"], ac["vo_count"]
+            done_blocks = C.c_void_p(vo_count.data_ptr() + 4)
+            _lib.check(L.rvo3d_reader_zero_features(p(x), x.stride(0), E * N, zp["state_dim"], zp["feat_dim"],
+                                                    p(zp["ln_w"]), p(zp["ln_b"]), zp["sum_h0"], zp["sumsq_h0"],
+                                                    zp["eps"], p(f0), f0.stride(0), p(cnt), p(ac["vo_list"]),
+                                                    p(vo_count), stream()), "rvo3d_reader_zero_features")
+            _lib.check(L.rvo3d_policy_mlp_sample(p(zp["blob"]), zp["width"], p(f0), f0.stride(0), E * N, None, 0, 0,
+                                                 1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
+                                                 step_arg(), *out, None, None, stream()), "rvo3d_policy_mlp_sample")
+            if tb is not None:
+                _lib.check(L.rvo3d_policy_rnn_tiles(
+                    p(tb["blob"]), tb["blob_bytes"], tb["hidden"], tb["in_dim"], tb["state_dim"], tb["bidir"], p(x),
+                    x.stride(0), p(cnt), p(ac["vo_list"]), p(vo_count), done_blocks, p(ac["tiles_work"]), E * N, slots,
+                    1 if tb["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(), *out, None, stream()),
+                    "rvo3d_policy_rnn_tiles")
+            else:
+                _lib.check(L.rvo3d_policy_rows(C.byref(zp["rows_net"]), p(x), x.stride(0), p(cnt), p(ac["vo_list"]),
+                                               p(vo_count), done_blocks, 1 if zp["tanh"] else 0, p(log_std), 1.0,
+                                               self._sample_seed, step_arg(), *out, stream()), "rvo3d_policy_rows")
+
+        def policy_direct(x, cnt, out):
+            mu, v = self._mu_v(x, cnt.view(E * N))
+            hd = _lib.PolicyHeads(mu.data_ptr(), v.data_ptr(), mu.stride(0), 1, _lib.RVO3D_F32, 0, 0, 0,
+                                  None, None, None, None, log_std.data_ptr())
+            _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"], *out, None, None,
+                                             stream()), "rvo3d_policy_sample")
+
+        def policy_heads(x, cnt, out):
+            # the first layer's A operand: mlp_ac - the observation cast into a zero-padded buffer (ONE kernel);
+            # rnn_ac - the reader's features (rvo3d_reader_first_step + the few rows with several VO rows)
+            xc = self.ac.prepare_input(x, cnt.view(E * N), plan, ac)
+            with torch.no_grad(), self._tuned_gemms():
+                hp, hv = self.ac.hidden_pair(xc, plan)
+            hd = _lib.PolicyHeads(hp.data_ptr(), hv.data_ptr(), hp.stride(0), hv.stride(0),
+                                  _lib.RVO3D_BF16 if dt == torch.bfloat16 else _lib.RVO3D_F32, plan["hidden"],
+                                  1 if plan["tanh"] else 0, 0, plan["w_pi"].data_ptr(), plan["b_pi"].data_ptr(),
+                                  plan["w_v"].data_ptr(), plan["b_v"].data_ptr(), log_std.data_ptr())
+            # (the generator's counter is (row, call number): every call draws fresh noise)
+            _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"], *out, None, None,
+                                             stream()), "rvo3d_policy_sample")
+
+        policy = {"mlp": policy_mlp, "mlp_x3": policy_mlp, "rnn0": policy_rnn0, "rnn_tiles": policy_rnn0,
+                  "direct": policy_direct, "heads": policy_heads}[mode]
+
         def launches(t, epoch_ended):
-            x = buf.obs[t].view(E * N, env.W)
-            act_t, logp_t, val_t = buf.act[t].view(E * N, 3), buf.logp[t].view(E * N), buf.val[t].view(E * N)
-            if mode in ("mlp", "mlp_x3"):
-                # (the env's counts: column groups that are zero for all rows of a wave are skipped)
-                fn = L.rvo3d_policy_mlp_sample if mode == "mlp" else L.rvo3d_policy_mlp_x3_sample
-                _lib.check(fn(p(mb["blob"]), env.W, p(x), x.stride(0), E * N,
-                              p(buf.cnt[t]), 12, 9, 1 if mb["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
-                              step_arg(), p(act_t), p(logp_t), p(val_t), None, None, stream()),
-                           "rvo3d_policy_mlp_sample" if mode == "mlp" else "rvo3d_policy_mlp_x3_sample")
-                ac["step"] += 1
-            if mode in ("rnn0", "rnn_tiles"):
-                # rows without a velocity-obstacle row: collapsed first layer (rvo3d_reader_zero_features builds its 20
-                # inputs and lists the rows that do have VO rows) + the MFMA kernel; the listed rows: one workgroup each,
-                # as the modules compute them; no host synchronisation
-                if "feat0" not in ac or ac["feat0"].shape != (E * N, zp["width"]):
-                    ac["feat0"] = torch.empty((E * N, zp["width"]), dtype=torch.float32, device=self.device)
-                    ac["vo_list"] = torch.zeros(E * N, dtype=torch.int32, device=self.device)
-                    ac["vo_count"] = torch.zeros(2, dtype=torch.int32, device=self.device)   # [count, finished workgroups]
-                f0, cnt_t = ac["feat0"], buf.cnt[t]
-                _lib.check(L.rvo3d_reader_zero_features(p(x), x.stride(0), E * N, zp["state_dim"], zp["feat_dim"],
-                                                        p(zp["ln_w"]), p(zp["ln_b"]), zp["sum_h0"], zp["sumsq_h0"],
-                                                        zp["eps"], p(f0), f0.stride(0), p(cnt_t), p(ac["vo_list"]),
-                                                        p(ac["vo_count"]), stream()), "rvo3d_reader_zero_features")
-                _lib.check(L.rvo3d_policy_mlp_sample(p(zp["blob"]), zp["width"], p(f0), f0.stride(0), E * N, None, 0, 0,
-                                                     1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
-                                                     step_arg(), p(act_t), p(logp_t), p(val_t), None, None, stream()),
-                           "rvo3d_policy_mlp_sample")
-                slots = env.nm if hasattr(env, "nm") else (env.W - zp["state_dim"]) // 9
-                if mode == "rnn_tiles":
-                    # the listed rows in 32-row MFMA tiles, grouped by their VO count on the device
-                    nw = int(L.rvo3d_policy_rnn_tiles_work_bytes(E * N, slots)) // 4
-                    if "tiles_work" not in ac or ac["tiles_work"].numel() != nw:
-                        ac["tiles_work"] = torch.zeros(nw, dtype=torch.int32, device=self.device)
-                    _lib.check(L.rvo3d_policy_rnn_tiles(
-                        p(tb["blob"]), tb["blob_bytes"], tb["hidden"], tb["in_dim"], tb["state_dim"], tb["bidir"], p(x),
-                        x.stride(0), p(cnt_t), p(ac["vo_list"]), p(ac["vo_count"]), C.c_void_p(ac["vo_count"].data_ptr() + 4),
-                        p(ac["tiles_work"]), E * N, slots, 1 if tb["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
-                        step_arg(), p(act_t), p(logp_t), p(val_t), None, stream()), "rvo3d_policy_rnn_tiles")
-                else:
-                    net = zp["rows_net"]
-                    net.slots = slots
-                    _lib.check(L.rvo3d_policy_rows(C.byref(net), p(x), x.stride(0), p(cnt_t), p(ac["vo_list"]),
-                                                   p(ac["vo_count"]), C.c_void_p(ac["vo_count"].data_ptr() + 4),
-                                                   1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(),
-                                                   p(act_t), p(logp_t), p(val_t), stream()), "rvo3d_policy_rows")
-                ac["step"] += 1
-            if mode == "direct":
-                mu, v = self._mu_v(x, buf.cnt[t].view(E * N))
-                hd = _lib.PolicyHeads(mu.data_ptr(), v.data_ptr(), mu.stride(0), 1, _lib.RVO3D_F32, 0, 0, 0,
-                                      None, None, None, None, log_std.data_ptr())
-                _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"],
-                                                 p(act_t), p(logp_t), p(val_t), None, None, stream()),
-                           "rvo3d_policy_sample")
-                ac["step"] += 1
-                del mu, v
-            plan = self.ac.fused_plan(dt) if mode == "heads" else None
-            # (rollout_chunk: the policy can run over the rows in chunks whose activations stay in the 256 MiB
-            # Infinity Cache.  Measured at 64 x 4096, bf16: no gain - 422 / 420 / 427 / 555 us per step for all /
-            # 131072 / 65536 / 32768 rows per pass; the [rows, 256] x [256, 256] GEMMs take 20 us per 65536 rows
-            # either way: they are not bound by HBM.  Off by default.)
-            B = E * N
-            Cn = B if not self.rollout_chunk else min(B, int(self.rollout_chunk))
-            for r0 in (range(0, B, Cn) if mode == "heads" else ()):
-                n = min(Cn, B - r0)
-                # the first layer's A operand: mlp_ac - the observation cast into a zero-padded buffer (ONE kernel);
-                # rnn_ac - the reader's features (rvo3d_reader_first_step + the few rows with several VO rows)
-                xc = self.ac.prepare_input(x[r0:r0 + n], buf.cnt[t].view(E * N)[r0:r0 + n], plan, ac)
-                with torch.no_grad(), self._tuned_gemms():
-                    hp, hv = self.ac.hidden_pair(xc, plan)
-                hd = _lib.PolicyHeads(hp.data_ptr(), hv.data_ptr(), hp.stride(0), hv.stride(0),
-                                      _lib.RVO3D_BF16 if dt == torch.bfloat16 else _lib.RVO3D_F32, plan["hidden"],
-                                      1 if plan["tanh"] else 0, 0, plan["w_pi"].data_ptr(), plan["b_pi"].data_ptr(),
-                                      plan["w_v"].data_ptr(), plan["b_v"].data_ptr(), self.ac.log_std.data_ptr())
-                # (the generator's counter is (row of the chunk, call number): every call draws fresh noise)
-                _lib.check(L.rvo3d_policy_sample(C.byref(hd), n, 1.0, self._sample_seed, ac["step"],
-                                                 p(act_t[r0:]), p(logp_t[r0:]), p(val_t[r0:]), None, None, stream()),
-                           "rvo3d_policy_sample")
-                ac["step"] += 1
-                del hp, hv
+            policy(buf.obs[t].view(E * N, env.W), buf.cnt[t], (p(buf.act[t]), p(buf.logp[t]), p(buf.val[t])))
+            ac["step"] += 1  # (the noise counter: one per step in every mode)
             # the env steps from the stored (rounded) action: rounding twice is rounding once
             env.step_policy(buf.act[t], autoreset=True, obs_out=buf.obs[t + 1], cnt_out=buf.cnt[t + 1])
             _lib.check(L.rvo3d_rollout_account(E, N, p(env.reward), p(env.done), p(env.finish),

@@ -88,16 +88,44 @@ def _hidden_pair(x, plan):
     return hp, hv
 
 
-def _plan_cached(module, dtype, build):
-    """`build()` once per (dtype, parameter versions, parameter storages) of `module`."""
-    params = list(module.parameters())
-    key = (dtype, tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
-    hit = getattr(module, "_plan", None)
+def _plan_cached(module, attr, params, build, tag=None):
+    """`build(previous value or None)` once per (tag, versions, storages) of `params`, kept in `module.<attr>`: an
+    optimizer step (in place: a new version) or a new storage rebuilds it; a rebuild may reuse the previous value's
+    allocations."""
+    key = (tag, tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
+    hit = getattr(module, attr, None)
     if hit is not None and hit[0] == key:
         return hit[1]
-    plan = build()
-    module._plan = (key, plan)
-    return plan
+    out = build(None if hit is None else hit[1])
+    setattr(module, attr, (key, out))
+    return out
+
+
+def _layers(*nets):
+    """([the nn.Linear layers], [the other modules]) of each of `nets`."""
+    return ([[m for m in n if isinstance(m, nn.Linear)] for n in nets],
+            [[m for m in n if not isinstance(m, nn.Linear)] for n in nets])
+
+
+def _relu_256_heads(lins, acts):
+    """Whether an actor / critic pair (_layers) is what the fused policy kernels are written for: three layers with
+    biases each, -> 256 -> 256 -> 3 / -> 1, ReLU between them, Tanh or Identity behind the actor, Identity behind the
+    critic."""
+    return (all(len(l) == 3 and all(m.bias is not None for m in l) for l in lins) and all(acts)
+            and [m.out_features for m in lins[0]] == [256, 256, 3] and [m.out_features for m in lins[1]] == [256, 256, 1]
+            and all(isinstance(m, nn.ReLU) for a in acts for m in a[:-1])
+            and isinstance(acts[0][-1], (nn.Tanh, nn.Identity)) and isinstance(acts[1][-1], nn.Identity))
+
+
+def _zero_input_h0(reader, device):
+    """The GRU's hidden state for a zero input from h = 0 (both directions summed), float64 [hidden]: the reader's
+    state for every row without a velocity-obstacle row."""
+    with torch.no_grad():
+        z = torch.zeros((1, reader.input_dim), device=device)
+        h0 = reader._gru_first(z, "")
+        if reader.mode == "biGRU":
+            h0 = h0 + reader._gru_first(z, "_reverse")
+        return h0.reshape(-1).double()
 
 
 def collapsed_first_layer(reader, lin, h0=None):
@@ -107,13 +135,9 @@ def collapsed_first_layer(reader, lin, h0=None):
     the LayerNorm's affine,  lin(LayerNorm(concat(p, h0))) = W_p f_p + rstd a - (mean rstd) b + c  with
     f_p = (p - mean) rstd g_p + bt_p,  a = W_h (h0 g_h),  b = W_h g_h,  c = W_h bt_h + bias.  Returns (W_p, a, b, c)."""
     sd = reader.state_dim
+    if h0 is None:
+        h0 = _zero_input_h0(reader, lin.weight.device)
     with torch.no_grad():
-        if h0 is None:
-            z = torch.zeros((1, reader.input_dim), device=lin.weight.device)
-            h0 = reader._gru_first(z, "")
-            if reader.mode == "biGRU":
-                h0 = h0 + reader._gru_first(z, "_reverse")
-            h0 = h0.reshape(-1).double()
         g, bt = reader.ln.weight.double(), reader.ln.bias.double()
         W1, b1 = lin.weight.double(), lin.bias.double()
         Wh = W1[:, sd:]
@@ -359,14 +383,18 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
                         use_gpu=use_gpu)
 
     # ---- rollout fast path (rvo3d_amd.policy.multi_ppo._collect_fused, "heads" mode) ----
+    def _gru_reader(self):
+        """The reader when actor and critic share one GRU / biGRU reader (the fused paths' premise), else None."""
+        r = self.pi.rnn_reader
+        return r if r is not None and r is self.v.rnn_reader and r.mode in ("GRU", "biGRU") else None
+
     def fused_plan(self, dtype):
         """The reader's weights as rvo3d_reader_first_step wants them (float32) + the MLP pair plan of actor and critic
         on the reader's features; None when the architecture has no fast path (LSTM reader, separate readers, a hidden
         width or input width the kernel has no instantiation for, non-ReLU stacks)."""
-        def build():
-            r = self.pi.rnn_reader
-            if (r is None or r is not self.v.rnn_reader or r.mode not in ("GRU", "biGRU") or r.input_dim != 9
-                    or r.state_dim > 32 or r.hidden_dim not in (64, 128, 192, 256)):
+        def build(_prev):
+            r = self._gru_reader()
+            if r is None or r.input_dim != 9 or r.state_dim > 32 or r.hidden_dim not in (64, 128, 192, 256):
                 return None
             plan = _mlp_pair_plan(self.pi.net_out, self.v.v_net, dtype)
             if plan is None or plan["k_in"] != r.state_dim + r.hidden_dim:
@@ -380,7 +408,7 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
                 b_hh_r=f32(g.bias_hh_l0_reverse) if r.mode == "biGRU" else None,
                 ln_w=f32(r.ln.weight), ln_b=f32(r.ln.bias), eps=float(r.ln.eps))
             return plan
-        return _plan_cached(self, dtype, build)
+        return _plan_cached(self, "_plan", list(self.parameters()), build, tag=dtype)
 
     def zero_vo_plan(self):
         """Weights for the rollout's fastest path (multi_ppo._collect_fused, mode "rnn0"): rows WITHOUT a velocity-obstacle
@@ -390,76 +418,64 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
         rvo3d_reader_zero_features + rvo3d_policy_mlp_sample.  Returns dict(blob, width, sum_h0, sumsq_h0, ln_w, ln_b,
         eps, feat_dim, tanh), rebuilt when a parameter changed; None when the architecture does not fit (LSTM or separate
         readers, heads other than ReLU (256, 256) stacks, not on a GPU)."""
-        r = self.pi.rnn_reader
-        if (r is None or r is not self.v.rnn_reader or r.mode not in ("GRU", "biGRU") or r.state_dim > 16
-                or r.hidden_dim > 256 or r.input_dim > 16 or next(self.parameters()).device.type != "cuda"):
+        r = self._gru_reader()
+        if (r is None or r.state_dim > 16 or r.hidden_dim > 256 or r.input_dim > 16
+                or next(self.parameters()).device.type != "cuda"):
             return None
-        nets = (self.pi.net_out, self.v.v_net)
-        lins = [[m for m in n if isinstance(m, nn.Linear)] for n in nets]
-        acts = [[m for m in n if not isinstance(m, nn.Linear)] for n in nets]
+        lins, acts = _layers(self.pi.net_out, self.v.v_net)
         D = r.state_dim + r.hidden_dim
-        if (any(len(l) != 3 for l in lins) or [m.out_features for m in lins[0]] != [256, 256, 3]
-                or [m.out_features for m in lins[1]] != [256, 256, 1] or any(l[0].in_features != D for l in lins)
-                or not all(isinstance(m, nn.ReLU) for a in acts for m in a[:-1])
-                or not isinstance(acts[0][-1], (nn.Tanh, nn.Identity)) or not isinstance(acts[1][-1], nn.Identity)
-                or any(m.bias is None for l in lins for m in l)):
+        if not _relu_256_heads(lins, acts) or any(l[0].in_features != D for l in lins):
             return None
         params = list(self.parameters())
-        key = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
-        hit = getattr(self, "_zero_plan", None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        import ctypes as C
-        from .. import _lib
-        L = _lib.lib()
-        dev = params[0].device
-        sd, width = r.state_dim, r.state_dim + 8
-        bf = torch.bfloat16
-        with torch.no_grad():
-            z = torch.zeros((1, r.input_dim), device=dev)
-            h0 = r._gru_first(z, "")
-            if r.mode == "biGRU":
-                h0 = h0 + r._gru_first(z, "_reverse")
-            h0 = h0.reshape(-1).double()
-            keep = []
-            for l in lins:
-                Wp, a, b, c = collapsed_first_layer(r, l[0], h0)
-                head = lambda x: x.float().to(bf).float()
-                cols = [Wp.float()]
-                for vec, sign in ((a, 1.0), (b, -1.0)):
-                    v = (sign * vec).float()
-                    cols += [head(v)[:, None], (v - head(v))[:, None], head(v)[:, None]]
-                cf = c.float()
-                cols += [head(cf)[:, None], (cf - head(cf))[:, None]]
-                keep += [torch.cat(cols, 1).contiguous(), torch.zeros(256, device=dev),
-                         l[1].weight.detach().float().contiguous(), l[1].bias.detach().float().contiguous(),
-                         l[2].weight.detach().float().contiguous(), l[2].bias.detach().float().contiguous()]
-            blob = hit[1]["blob"] if hit is not None else torch.empty(int(L.rvo3d_policy_mlp_blob_bytes(width)),
-                                                                       dtype=torch.uint8, device=dev)
-            wa = _lib.MlpWeights(*[t.data_ptr() for t in keep[:6]])
-            wb = _lib.MlpWeights(*[t.data_ptr() for t in keep[6:]])
-            with torch.cuda.device(dev):
-                _lib.check(L.rvo3d_policy_mlp_pack(C.byref(wa), C.byref(wb), width, C.c_void_p(blob.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                           "rvo3d_policy_mlp_pack")
-                torch.cuda.current_stream(dev).synchronize()  # (the temporaries above die with this scope)
-            # the modules' own tensors for rvo3d_policy_rows (the rows that do have VO rows): live parameters, no copies
-            gp = lambda n: getattr(r.rnn_net, n).data_ptr()
-            bi = r.mode == "biGRU"
-            rows_net = _lib.RnnPolicy(
-                gp("weight_ih_l0"), gp("weight_hh_l0"), gp("bias_ih_l0"), gp("bias_hh_l0"),
-                gp("weight_ih_l0_reverse") if bi else None, gp("weight_hh_l0_reverse") if bi else None,
-                gp("bias_ih_l0_reverse") if bi else None, gp("bias_hh_l0_reverse") if bi else None,
-                r.ln.weight.data_ptr(), r.ln.bias.data_ptr(), r.hidden_dim, r.input_dim, r.state_dim, 0, float(r.ln.eps), 0,
-                _lib.MlpWeights(*[t.data_ptr() for l in lins[0] for t in (l.weight, l.bias)]),
-                _lib.MlpWeights(*[t.data_ptr() for l in lins[1] for t in (l.weight, l.bias)]))
-            ok_rows = all(t.is_contiguous() and t.dtype == torch.float32 for t in params)
-            out = dict(blob=blob, width=width, sum_h0=float(h0.sum()), sumsq_h0=float((h0 * h0).sum()),
-                       rows_net=rows_net if ok_rows else None,
-                       ln_w=r.ln.weight.detach().float().contiguous(), ln_b=r.ln.bias.detach().float().contiguous(),
-                       eps=float(r.ln.eps), feat_dim=D, state_dim=sd, tanh=isinstance(acts[0][-1], nn.Tanh))
-        self._zero_plan = (key, out)
-        return out
+
+        def build(prev):
+            import ctypes as C
+            from .. import _lib
+            L = _lib.lib()
+            dev = params[0].device
+            width = r.state_dim + 8
+            bf = torch.bfloat16
+            h0 = _zero_input_h0(r, dev)
+            with torch.no_grad():
+                keep = []
+                for l in lins:
+                    Wp, a, b, c = collapsed_first_layer(r, l[0], h0)
+                    head = lambda x: x.float().to(bf).float()
+                    cols = [Wp.float()]
+                    for vec, sign in ((a, 1.0), (b, -1.0)):
+                        v = (sign * vec).float()
+                        cols += [head(v)[:, None], (v - head(v))[:, None], head(v)[:, None]]
+                    cf = c.float()
+                    cols += [head(cf)[:, None], (cf - head(cf))[:, None]]
+                    keep += [torch.cat(cols, 1).contiguous(), torch.zeros(256, device=dev),
+                             l[1].weight.detach().float().contiguous(), l[1].bias.detach().float().contiguous(),
+                             l[2].weight.detach().float().contiguous(), l[2].bias.detach().float().contiguous()]
+                blob = prev["blob"] if prev is not None else torch.empty(int(L.rvo3d_policy_mlp_blob_bytes(width)),
+                                                                         dtype=torch.uint8, device=dev)
+                wa = _lib.MlpWeights(*[t.data_ptr() for t in keep[:6]])
+                wb = _lib.MlpWeights(*[t.data_ptr() for t in keep[6:]])
+                with torch.cuda.device(dev):
+                    _lib.check(L.rvo3d_policy_mlp_pack(C.byref(wa), C.byref(wb), width, C.c_void_p(blob.data_ptr()),
+                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                               "rvo3d_policy_mlp_pack")
+                    torch.cuda.current_stream(dev).synchronize()  # (the temporaries above die with this scope)
+                # the modules' own tensors for rvo3d_policy_rows (the rows that do have VO rows): live parameters, no copies
+                gp = lambda n: getattr(r.rnn_net, n).data_ptr()
+                bi = r.mode == "biGRU"
+                rows_net = _lib.RnnPolicy(
+                    gp("weight_ih_l0"), gp("weight_hh_l0"), gp("bias_ih_l0"), gp("bias_hh_l0"),
+                    gp("weight_ih_l0_reverse") if bi else None, gp("weight_hh_l0_reverse") if bi else None,
+                    gp("bias_ih_l0_reverse") if bi else None, gp("bias_hh_l0_reverse") if bi else None,
+                    r.ln.weight.data_ptr(), r.ln.bias.data_ptr(), r.hidden_dim, r.input_dim, r.state_dim, 0,
+                    float(r.ln.eps), 0,
+                    _lib.MlpWeights(*[t.data_ptr() for l in lins[0] for t in (l.weight, l.bias)]),
+                    _lib.MlpWeights(*[t.data_ptr() for l in lins[1] for t in (l.weight, l.bias)]))
+                ok_rows = all(t.is_contiguous() and t.dtype == torch.float32 for t in params)
+                return dict(blob=blob, width=width, sum_h0=float(h0.sum()), sumsq_h0=float((h0 * h0).sum()),
+                            rows_net=rows_net if ok_rows else None,
+                            ln_w=r.ln.weight.detach().float().contiguous(), ln_b=r.ln.bias.detach().float().contiguous(),
+                            eps=float(r.ln.eps), feat_dim=D, state_dim=r.state_dim, tanh=isinstance(acts[0][-1], nn.Tanh))
+        return _plan_cached(self, "_zero_plan", params, build)
 
     def rnn_tiles_blob(self):
         """The packed weights of rvo3d_policy_rnn_tiles (the policy step of the rows WITH velocity-obstacle rows in 32-row
@@ -467,54 +483,44 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
         state_dim, bidir, tanh).  Its own cache entry, repacked when a parameter changed (version or storage); None when
         the architecture does not fit - a shared GRU / biGRU reader of hidden 64 or 256, in_dim 9, state_dim <= 16, ReLU
         (256, 256) stacks with 3 (Tanh or Identity) / 1 outputs, float32 parameters on a GPU."""
-        r = self.pi.rnn_reader
-        if (r is None or r is not self.v.rnn_reader or r.mode not in ("GRU", "biGRU") or r.hidden_dim not in (64, 256)
-                or r.input_dim != 9 or not 1 <= r.state_dim <= 16 or next(self.parameters()).device.type != "cuda"):
+        r = self._gru_reader()
+        if (r is None or r.hidden_dim not in (64, 256) or r.input_dim != 9 or not 1 <= r.state_dim <= 16
+                or next(self.parameters()).device.type != "cuda"):
             return None
-        nets = (self.pi.net_out, self.v.v_net)
-        lins = [[m for m in n if isinstance(m, nn.Linear)] for n in nets]
-        acts = [[m for m in n if not isinstance(m, nn.Linear)] for n in nets]
+        lins, acts = _layers(self.pi.net_out, self.v.v_net)
         D = r.state_dim + r.hidden_dim
-        if (any(len(l) != 3 for l in lins) or [m.out_features for m in lins[0]] != [256, 256, 3]
-                or [m.out_features for m in lins[1]] != [256, 256, 1] or any(l[0].in_features != D for l in lins)
-                or any(len(a) != 3 for a in acts)
-                or not all(isinstance(m, nn.ReLU) for a in acts for m in a[:-1])
-                or not isinstance(acts[0][-1], (nn.Tanh, nn.Identity)) or not isinstance(acts[1][-1], nn.Identity)
-                or any(m.bias is None for l in lins for m in l)
+        if (not _relu_256_heads(lins, acts) or any(l[0].in_features != D for l in lins) or any(len(a) != 3 for a in acts)
                 or any(p.dtype != torch.float32 for p in self.parameters())):
             return None
         params = list(self.parameters())
-        key = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
-        hit = getattr(self, "_tiles_blob", None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        import ctypes as C
-        from .. import _lib
-        L = _lib.lib()
-        bi = r.mode == "biGRU"
-        nbytes = int(L.rvo3d_policy_rnn_tiles_blob_bytes(r.hidden_dim, r.input_dim, r.state_dim, 1 if bi else 0))
-        dev = params[0].device
-        blob = hit[1]["blob"] if hit is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        g = r.rnn_net
-        keep = [t.detach().contiguous() for t in (
-            g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0) + ((
-            g.weight_ih_l0_reverse, g.weight_hh_l0_reverse, g.bias_ih_l0_reverse, g.bias_hh_l0_reverse) if bi else ()) + (
-            r.ln.weight, r.ln.bias)]
-        heads = [t.detach().contiguous() for l in lins for m in l for t in (m.weight, m.bias)]
-        ptr = [t.data_ptr() for t in keep]
-        rev = ptr[4:8] if bi else [None] * 4
-        net = _lib.RnnPolicy(*ptr[:4], *rev, *ptr[-2:], r.hidden_dim, r.input_dim, r.state_dim, 0, float(r.ln.eps), 0,
-                             _lib.MlpWeights(*[t.data_ptr() for t in heads[:6]]),
-                             _lib.MlpWeights(*[t.data_ptr() for t in heads[6:]]))
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev)
-            _lib.check(L.rvo3d_policy_rnn_tiles_pack(C.byref(net), C.c_void_p(blob.data_ptr()), nbytes,
-                                                     C.c_void_p(st.cuda_stream)), "rvo3d_policy_rnn_tiles_pack")
-            st.synchronize()  # (the contiguous copies above die with this scope)
-        out = dict(blob=blob, blob_bytes=nbytes, hidden=r.hidden_dim, in_dim=r.input_dim, state_dim=r.state_dim,
-                   bidir=1 if bi else 0, tanh=isinstance(acts[0][-1], nn.Tanh))
-        self._tiles_blob = (key, out)
-        return out
+
+        def build(prev):
+            import ctypes as C
+            from .. import _lib
+            L = _lib.lib()
+            bi = r.mode == "biGRU"
+            nbytes = int(L.rvo3d_policy_rnn_tiles_blob_bytes(r.hidden_dim, r.input_dim, r.state_dim, 1 if bi else 0))
+            dev = params[0].device
+            blob = prev["blob"] if prev is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            g = r.rnn_net
+            keep = [t.detach().contiguous() for t in (
+                g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0) + ((
+                g.weight_ih_l0_reverse, g.weight_hh_l0_reverse, g.bias_ih_l0_reverse, g.bias_hh_l0_reverse) if bi else ()) + (
+                r.ln.weight, r.ln.bias)]
+            heads = [t.detach().contiguous() for l in lins for m in l for t in (m.weight, m.bias)]
+            ptr = [t.data_ptr() for t in keep]
+            rev = ptr[4:8] if bi else [None] * 4
+            net = _lib.RnnPolicy(*ptr[:4], *rev, *ptr[-2:], r.hidden_dim, r.input_dim, r.state_dim, 0, float(r.ln.eps), 0,
+                                 _lib.MlpWeights(*[t.data_ptr() for t in heads[:6]]),
+                                 _lib.MlpWeights(*[t.data_ptr() for t in heads[6:]]))
+            with torch.cuda.device(dev):
+                st = torch.cuda.current_stream(dev)
+                _lib.check(L.rvo3d_policy_rnn_tiles_pack(C.byref(net), C.c_void_p(blob.data_ptr()), nbytes,
+                                                         C.c_void_p(st.cuda_stream)), "rvo3d_policy_rnn_tiles_pack")
+                st.synchronize()  # (the contiguous copies above die with this scope)
+            return dict(blob=blob, blob_bytes=nbytes, hidden=r.hidden_dim, in_dim=r.input_dim, state_dim=r.state_dim,
+                        bidir=1 if bi else 0, tanh=isinstance(acts[0][-1], nn.Tanh))
+        return _plan_cached(self, "_tiles_blob", params, build)
 
     def prepare_input(self, obs, cnt, plan, cache):
         """The reader's features [rows, Kp] as the A operand of the first MLP layer: rvo3d_reader_first_step for every
@@ -630,7 +636,12 @@ class mlp_ac(nn.Module):
         """Weights of the inference plan of `hidden_pair` (see _mlp_pair_plan), cached per parameter version (an
         optimizer step rebuilds them); None when the stacks are not ReLU MLPs of equal shape (the caller then takes
         the module path)."""
-        return _plan_cached(self, dtype, lambda: _mlp_pair_plan(self.pi_net, self.v_net, dtype))
+        return _plan_cached(self, "_plan", list(self.parameters()),
+                            lambda _prev: _mlp_pair_plan(self.pi_net, self.v_net, dtype), tag=dtype)
+
+    # precision -> (cache attribute, blob size query, pack entry point) of mlp_blob
+    _BLOBS = {"bf16": ("_blob", "rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_pack"),
+              "x3": ("_blob_x3", "rvo3d_policy_mlp_x3_blob_bytes", "rvo3d_policy_mlp_x3_pack")}
 
     def mlp_blob(self, precision="bf16"):
         """The packed weights of rvo3d_policy_mlp_sample (the whole policy step in ONE kernel on the matrix cores:
@@ -638,42 +649,29 @@ class mlp_ac(nn.Module):
         is written for - ReLU MLPs obs_width -> 256 -> 256 -> 3 (Tanh or Identity) / -> 1, obs_width <= 126, on a GPU.
         precision="x3": the blob of rvo3d_policy_mlp_x3_sample (split-bf16 products, float32-class:
         csrc/rvo3d_policy_mlp_x3.hpp).  Each precision has its own cache entry."""
-        if precision not in ("bf16", "x3"):
+        if precision not in self._BLOBS:
             raise ValueError(f"precision must be 'bf16' or 'x3', not {precision!r}")
-        pl = [m for m in self.pi_net if isinstance(m, nn.Linear)]
-        vl = [m for m in self.v_net if isinstance(m, nn.Linear)]
-        pa = [m for m in self.pi_net if not isinstance(m, nn.Linear)]
-        va = [m for m in self.v_net if not isinstance(m, nn.Linear)]
-        if (len(pl) != 3 or len(vl) != 3 or self.obs_width > 126 or pl[0].weight.device.type != "cuda"
-                or [m.out_features for m in pl] != [256, 256, 3] or [m.out_features for m in vl] != [256, 256, 1]
-                or not all(isinstance(m, nn.ReLU) for m in pa[:-1] + va[:-1]) or len(pa) != 3 or len(va) != 3
-                or not isinstance(pa[-1], (nn.Tanh, nn.Identity)) or not isinstance(va[-1], nn.Identity)
-                or any(m.bias is None for m in pl + vl) or pl[0].weight.dtype != torch.float32):
+        lins, acts = _layers(self.pi_net, self.v_net)
+        if (self.obs_width > 126 or not _relu_256_heads(lins, acts) or any(len(a) != 3 for a in acts)
+                or lins[0][0].weight.device.type != "cuda" or lins[0][0].weight.dtype != torch.float32):
             return None
-        params = list(self.pi_net.parameters()) + list(self.v_net.parameters())
-        key = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
-        attr = "_blob" if precision == "bf16" else "_blob_x3"
-        hit = getattr(self, attr, None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        import ctypes as C
-        from .. import _lib
-        L = _lib.lib()
-        nbytes = L.rvo3d_policy_mlp_blob_bytes if precision == "bf16" else L.rvo3d_policy_mlp_x3_blob_bytes
-        pack = L.rvo3d_policy_mlp_pack if precision == "bf16" else L.rvo3d_policy_mlp_x3_pack
-        dev = pl[0].weight.device
-        blob = hit[1]["blob"] if hit is not None else torch.empty(int(nbytes(self.obs_width)), dtype=torch.uint8,
-                                                                   device=dev)
-        keep = [t.detach().contiguous() for lin in (pl, vl) for m in lin for t in (m.weight, m.bias)]
-        a = _lib.MlpWeights(*[t.data_ptr() for t in keep[:6]])
-        b = _lib.MlpWeights(*[t.data_ptr() for t in keep[6:]])
-        with torch.cuda.device(dev):
-            _lib.check(pack(C.byref(a), C.byref(b), self.obs_width, C.c_void_p(blob.data_ptr()),
-                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                       "rvo3d_policy_mlp_pack" if precision == "bf16" else "rvo3d_policy_mlp_x3_pack")
-        out = dict(blob=blob, tanh=isinstance(pa[-1], nn.Tanh))
-        setattr(self, attr, (key, out))
-        return out
+        attr, nbytes, pack = self._BLOBS[precision]
+
+        def build(prev):
+            import ctypes as C
+            from .. import _lib
+            L = _lib.lib()
+            dev = lins[0][0].weight.device
+            blob = prev["blob"] if prev is not None else torch.empty(int(getattr(L, nbytes)(self.obs_width)),
+                                                                     dtype=torch.uint8, device=dev)
+            keep = [t.detach().contiguous() for lin in lins for m in lin for t in (m.weight, m.bias)]
+            a = _lib.MlpWeights(*[t.data_ptr() for t in keep[:6]])
+            b = _lib.MlpWeights(*[t.data_ptr() for t in keep[6:]])
+            with torch.cuda.device(dev):
+                _lib.check(getattr(L, pack)(C.byref(a), C.byref(b), self.obs_width, C.c_void_p(blob.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), pack)
+            return dict(blob=blob, tanh=isinstance(acts[0][-1], nn.Tanh))
+        return _plan_cached(self, attr, list(self.pi_net.parameters()) + list(self.v_net.parameters()), build)
 
     def prepare_input(self, obs, cnt, plan, cache):
         """The A operand of the first-layer GEMM: the observation itself (float32) or - ONE kernel - its cast into a

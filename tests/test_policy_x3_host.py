@@ -119,3 +119,33 @@ def test_split_bf16_error_model(width):
     with torch.no_grad():
         z32 = ac.pi_net[:-1](x).double()
     assert float((z32 - z64).abs().max()) < 1e-5
+
+
+@pytest.mark.parametrize("name", ["rvo3d_policy_mlp", "rvo3d_policy_mlp_x3"])
+def test_mlp_entry_points_reject_bad_arguments_before_any_launch(name):
+    """The argument checks of the bf16 and x3 entry points (one implementation in csrc/rvo3d_capi.hip) on the CPU: fake
+    aligned pointers, never dereferenced - every call below fails its checks, or has no rows, before touching a GPU."""
+    import ctypes as C
+    _lib.build_hip()
+    L = _lib.lib()
+    fake = lambda n: C.c_void_p(4096 * n)
+    sample, pack, nbytes = (getattr(L, name + s) for s in ("_sample", "_pack", "_blob_bytes"))
+    W, rows = 102, 200
+    args = lambda **k: [k.get("blob", fake(1)), k.get("W", W), fake(2), k.get("ld", W), k.get("rows", rows), None, 12, 9,
+                        1, fake(3), 1.0, 0, 0, fake(4), fake(5), fake(6), None, None, None]
+    assert sample(*args(W=127)) == -1 and b"obs_width" in L.rvo3d_last_error()
+    assert sample(*args(ld=W - 1)) == -1 and b"obs_ld" in L.rvo3d_last_error()
+    assert sample(*args(blob=C.c_void_p(4096 + 4))) == -1 and b"aligned" in L.rvo3d_last_error()
+    assert sample(*args(rows=-1)) == -1 and b"rows" in L.rvo3d_last_error()
+    assert sample(*args(blob=None)) == -1 and b"null" in L.rvo3d_last_error()
+    assert sample(*args(rows=0)) == 0
+    assert nbytes(127) == -1 and nbytes(0) == -1
+    assert nbytes(102) == {"rvo3d_policy_mlp": 2 * (7 * 8192 + 131072 + 1024 + 2048 + 16),
+                           "rvo3d_policy_mlp_x3": 2 * (7 * 16384 + 131072 + 1024 + 4096 + 131072 + 16)}[name]
+    w = _lib.MlpWeights(*[fake(10 + i) for i in range(6)])
+    assert pack(None, C.byref(w), W, fake(1), None) == -1 and b"null" in L.rvo3d_last_error()
+    assert pack(C.byref(w), C.byref(w), 127, fake(1), None) == -1 and b"obs_width" in L.rvo3d_last_error()
+    assert pack(C.byref(w), C.byref(w), W, C.c_void_p(4096 + 8), None) == -1 and b"aligned" in L.rvo3d_last_error()
+    bad = _lib.MlpWeights.from_buffer_copy(w)
+    bad.w2 = None
+    assert pack(C.byref(w), C.byref(bad), W, fake(1), None) == -1 and b"weight" in L.rvo3d_last_error()

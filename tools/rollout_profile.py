@@ -15,7 +15,6 @@ ap.add_argument("--drones", type=int, default=64)
 ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--fp32", action="store_true")
 ap.add_argument("--policy", default="mlp", help="mlp | rnn (the reference's biGRU actor-critic, 256 hidden)")
-ap.add_argument("--chunk", type=int, default=0, help="rows per policy pass (0: all at once)")
 ap.add_argument("--tunable", action="store_true", help="torch.cuda.tunable: let TunableOp pick the hipBLASLt solution per GEMM shape")
 ap.add_argument("--module-path", action="store_true", help="the unfused loop (PyTorch glue)")
 args = ap.parse_args()
@@ -33,7 +32,7 @@ else:
     ac = rnn_ac(None, Space(), 12, 9, 256, (256, 256), (256, 256), torch.nn.ReLU, torch.nn.Tanh, torch.nn.Identity,
                 use_gpu=False, rnn_mode="biGRU").cuda()
 tr = multi_ppo(env, ac, steps_per_epoch=args.steps, max_ep_len=500, amp=not args.fp32,
-               fused_rollout=not args.module_path, rollout_chunk=args.chunk,
+               fused_rollout=not args.module_path,
                graph_rollout=False)   # (eager launches: the profiler lists the kernels of a step)
 env.reset(); env.observe()
 tr.collect(final_reset=False); tr.buf.ptr = 0
