@@ -188,7 +188,10 @@ class multi_ppo:
         self.fused_rnn_tiles = bool(fused_rnn_tiles)
         # the fast paths' per-step launches replayed as HIP graphs from the second rollout on (see _collect_fused);
         # opt-in: measured at 64 x 4096, 0.158 ms per step with and 0.157-0.161 without - the gaps between the dependent
-        # kernels of a graph are what they are between stream launches
+        # kernels of a graph are what they are between stream launches.  Across update(): the "mlp" graphs survive an
+        # optimizer step (all their arguments are addresses, the blob is repacked in place before the replay); the "rnn0"
+        # graphs do not (they hold the plan's LayerNorm sums by value): the rollout after an update() captures them
+        # again.  A parameter that moved to another storage drops the graphs of either mode.
         self.graph_rollout = bool(graph_rollout)
         # the rollout's policy GEMMs ([E*N, 128] x [128, 512], [E*N, 256] x [256, 256], bf16) through PyTorch's
         # TunableOp: the first call of a shape times hipBLASLt's candidate kernels (<= 3 s per shape) and keeps
@@ -382,6 +385,16 @@ class multi_ppo:
             if getattr(self, "_step_dev", None) is None:
                 self._step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
                 self._graphs = {}
+            # what a captured launch holds of the parameters beyond the buffers' addresses: the address of every live
+            # parameter ("rnn0": the rows_net struct, by value; both modes: log_std), and in "rnn0" the plan's sum_h0 /
+            # sumsq_h0 as host floats, which change with every parameter version although zero_vo_plan() repacks its
+            # blob in place - graphs captured from other storages or, in "rnn0", other versions are dropped
+            params = list(self.ac.parameters())
+            held = (mode, tuple(q.data_ptr() for q in params),
+                    tuple(q._version for q in params) if mode == "rnn0" else None)
+            if getattr(self, "_graphs_held", None) != held:
+                self._graphs.clear()
+                self._graphs_held = held
             _lib.check(L.rvo3d_rollout_set_step_counter(p(self._step_dev)), "rvo3d_rollout_set_step_counter")
         step_arg = lambda: (1 << 32) if (use_graph and not getattr(self, "_graph_failed", False)) else ac["step"]
 
@@ -477,22 +490,25 @@ class multi_ppo:
                     return launches(t, epoch_ended)
             g.replay()
 
-        for t in range(T):
-            epoch_ended = final_reset and t == T - 1
-            one_step(t, epoch_ended)
-            since_full_reset += 1
-            buf.ptr += 1
-            # only now can an episode have timed out (no episode is longer than the steps since the last
-            # full reset): before that the device is not asked (no synchronisation in the loop)
-            # (any_extra is sticky: the kernel only ever sets it, and it is cleared here once its drones are
-            # handled - one launch per step less than clearing it before every step; a timeout cannot occur, and
-            # the flag cannot be set, before since_full_reset exceeds max_ep_len or the epoch ends)
-            if epoch_ended or (since_full_reset > self.max_ep_len and int(ac["any_extra"].item()) != 0):
-                env.reset_drones(ac["extra"])
-                env.observe(obs_out=buf.obs[t + 1], cnt_out=buf.cnt[t + 1])
-                ac["any_extra"].zero_()
-        if use_graph:
-            _lib.check(L.rvo3d_rollout_set_step_counter(None), "rvo3d_rollout_set_step_counter")
+        try:
+            for t in range(T):
+                epoch_ended = final_reset and t == T - 1
+                one_step(t, epoch_ended)
+                since_full_reset += 1
+                buf.ptr += 1
+                # only now can an episode have timed out (no episode is longer than the steps since the last
+                # full reset): before that the device is not asked (no synchronisation in the loop)
+                # (any_extra is sticky: the kernel only ever sets it, and it is cleared here once its drones are
+                # handled - one launch per step less than clearing it before every step; a timeout cannot occur, and
+                # the flag cannot be set, before since_full_reset exceeds max_ep_len or the epoch ends)
+                if epoch_ended or (since_full_reset > self.max_ep_len and int(ac["any_extra"].item()) != 0):
+                    env.reset_drones(ac["extra"])
+                    env.observe(obs_out=buf.obs[t + 1], cnt_out=buf.cnt[t + 1])
+                    ac["any_extra"].zero_()
+        finally:
+            # (also when a step raised: the counter is process-global, every later sampling launch would add it)
+            if use_graph:
+                _lib.check(L.rvo3d_rollout_set_step_counter(None), "rvo3d_rollout_set_step_counter")
         buf.cut[:T] |= ac["cut"].bool()
         self._cur = (buf.obs[T], buf.cnt[T])
         if mode == "rnn0":
