@@ -10,7 +10,7 @@
 // batch row on the lane and the hidden unit in the 16 accumulator registers, and the next layer - which sums over
 // hidden units - takes the converted accumulators as its B fragments as they are: no LDS, no lane movement between
 // layers (the k order inside a 16-wide step is permuted, element j of lane half h is unit 8 (j >> 2) + 4 h + (j & 3):
-// the packed weights of the following layer are stored in that order).  A wave takes 32 batch rows at a time through all layers (28 + 64 registers of bf16
+// the packed weights of the following layer are stored in that order, mfma_k_perm).  A wave takes 32 batch rows at a time through all layers (28 + 64 registers of bf16
 // activations, 16 + 16 of accumulators) and finishes 64 rows - two passes - at once, one row per lane.
 //
 // Weights.  One workgroup (8 waves, one per CU: 2 per SIMD) serves ONE of the two networks and keeps in LDS, for its
@@ -30,16 +30,10 @@
 
 #include <type_traits>
 
+#include "rvo3d_mfma_tiles.hpp"
 #include "rvo3d_rollout_kernels.hpp"
 
 namespace rvo3d {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMlpH = 256;                                   // hidden width of both layers
 constexpr int kMlpW2Bytes = 8 * 16 * 1024;                   // [8 tiles][16 k-steps][64 lanes][8] bf16
@@ -51,9 +45,6 @@ __host__ __device__ constexpr int mlp_ks1(int k_in) { return (k_in + 1 + 15) / 1
 __host__ __device__ constexpr int64_t mlp_net_bytes(int ks1) {
   return (int64_t)8 * ks1 * 1024 + kMlpResidentBytes + kMlpHeadBiasBytes;
 }
-// hidden unit (within a 32-unit tile) that accumulator register i of lane half h holds
-__host__ __device__ constexpr int mlp_acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
 // ---- packing: nn.Linear weights (float32, [out][in]) -> the fragments the kernel reads ----------------------------
 struct MlpPackArgs {
   int32_t k_in, ks1;
@@ -65,10 +56,11 @@ struct MlpPackArgs {
   const float* b3[2];  // [3] / [1]
   unsigned char* blob;  // 2 x mlp_net_bytes(ks1)
 };
-__global__ void __launch_bounds__(256) mlp_pack_kernel(const MlpPackArgs A) {
-  const int net = blockIdx.y;
-  const int64_t nb = mlp_net_bytes(A.ks1);
-  unsigned char* const blob = A.blob + net * nb;
+// The elements of one network's blob as (section, index in the section's logical array, value): the index decoding and
+// the weight lookup of both packs (mlp_pack_kernel here, mlp_x3_pack_kernel); store(section, i, v) places an element.
+enum MlpPackSection { kPackW1, kPackW2, kPackB2, kPackW3, kPackHeadBias };
+template <class Store>
+__device__ __forceinline__ void mlp_pack_elements(const MlpPackArgs& A, int net, Store store) {
   const int n_w1 = 8 * A.ks1 * 512, n_w2 = 8 * 16 * 512, n_b2 = 256, n_w3 = 16 * 4 * 2 * 8, n_hb = 4;
   const int total = n_w1 + n_w2 + n_b2 + n_w3 + n_hb;
   for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
@@ -77,34 +69,47 @@ __global__ void __launch_bounds__(256) mlp_pack_kernel(const MlpPackArgs A) {
       const int j = i & 7, lane = (i >> 3) & 63, ms = i >> 9, s = ms % A.ks1, m = ms / A.ks1;
       const int row = 32 * m + (lane & 31), k = 16 * s + 8 * (lane >> 5) + j;
       const float v = k < A.k_in ? A.w1[net][(int64_t)row * A.k_in + k] : (k == A.k_in ? A.b1[net][row] : 0.f);
-      reinterpret_cast<uint16_t*>(blob)[i] = f32_to_bf16_rne(v);
+      store(kPackW1, i, v);
       continue;
     }
     i -= n_w1;
-    unsigned char* p = blob + (int64_t)8 * A.ks1 * 1024;
     if (i < n_w2) {  // [m2][t][lane][j]: W2[32 m2 + r][the unit the previous layer's fragment holds at (t, h, j)]
       const int j = i & 7, lane = (i >> 3) & 63, t = (i >> 9) & 15, m2 = i >> 13;
-      const int row = 32 * m2 + (lane & 31), k = 32 * (t >> 1) + 16 * (t & 1) + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3);
-      reinterpret_cast<uint16_t*>(p)[i] = f32_to_bf16_rne(A.w2[net][row * kMlpH + k]);
+      const int row = 32 * m2 + (lane & 31), k = mfma_k_perm(t, lane >> 5, j);
+      store(kPackW2, i, A.w2[net][row * kMlpH + k]);
       continue;
     }
-    i -= n_w2; p += kMlpW2Bytes;
+    i -= n_w2;
     if (i < n_b2) {  // [m2][h][reg]
       const int reg = i & 15, h = (i >> 4) & 1, m2 = i >> 5;
-      reinterpret_cast<float*>(p)[i] = A.b2[net][32 * m2 + mlp_acc_row(reg, h)];
+      store(kPackB2, i, A.b2[net][32 * m2 + mlp_acc_row(reg, h)]);
       continue;
     }
-    i -= n_b2; p += kMlpB2Bytes;
+    i -= n_b2;
     if (i < n_w3) {  // [t][row][h][j]
       const int j = i & 7, h = (i >> 3) & 1, tr = i >> 4, row = tr & 3, t = tr >> 2;
-      const int k = 32 * (t >> 1) + 16 * (t & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+      const int k = mfma_k_perm(t, h, j);
       const int n_out = net == 0 ? 3 : 1;
-      reinterpret_cast<uint16_t*>(p)[i] = f32_to_bf16_rne(row < n_out ? A.w3[net][row * kMlpH + k] : 0.f);
+      store(kPackW3, i, row < n_out ? A.w3[net][row * kMlpH + k] : 0.f);
       continue;
     }
-    i -= n_w3; p += kMlpW3Bytes;
-    reinterpret_cast<float*>(p)[i] = i < (net == 0 ? 3 : 1) ? A.b3[net][i] : 0.f;
+    i -= n_w3;
+    store(kPackHeadBias, i, i < (net == 0 ? 3 : 1) ? A.b3[net][i] : 0.f);
   }
+}
+__global__ void __launch_bounds__(256) mlp_pack_kernel(const MlpPackArgs A) {
+  const int net = blockIdx.y;
+  const int64_t nb = mlp_net_bytes(A.ks1);
+  unsigned char* const blob = A.blob + net * nb;
+  // the sections follow one another, each in its logical order: W1, W2 and W3 as bf16, b2 and the head bias as float
+  mlp_pack_elements(A, net, [&](int section, int i, float v) RVO3D_INLINE {
+    const int64_t w1_bytes = (int64_t)8 * A.ks1 * 1024;
+    const int64_t at[5] = {0, w1_bytes, w1_bytes + kMlpW2Bytes, w1_bytes + kMlpW2Bytes + kMlpB2Bytes,
+                           w1_bytes + kMlpResidentBytes};
+    unsigned char* const p = blob + at[section];
+    if (section == kPackB2 || section == kPackHeadBias) reinterpret_cast<float*>(p)[i] = v;
+    else reinterpret_cast<uint16_t*>(p)[i] = f32_to_bf16_rne(v);
+  });
 }
 
 // ---- the policy step ---------------------------------------------------------------------------------------------
@@ -119,19 +124,53 @@ struct PolicyMlpArgs {
   PolicySampleArgs S;         // tanh_out, log_std, std_factor, seed, step, rows, act / logp / val, dbg_*
 };
 
-__device__ __forceinline__ float relu_f32(float x) {
-  // ONE instruction beside the MFMAs (v_max_i32: as integers, negative floats are negative, positive ones keep their
-  // order).  fmaxf / fmed3 cost two - the compiler canonicalises the operand first -, and inline asm is out: the
-  // compiler pads the MFMA -> VALU read hazard for its own instructions only.
-  const int i = __builtin_bit_cast(int, x);
-  return __builtin_bit_cast(float, i > 0 ? i : 0);
+// ---- the frame both MLP kernels (policy_mlp_kernel here, policy_mlp_x3_kernel) stand in ---------------------------
+// Which rows a wave takes in which pass.  An aggregate of values the kernel computes in its own text, and the rest of
+// the frame (the workgroup -> (net, g, G) mapping, the row loads, the layer-1 dispatch, the tail) stays written out in
+// both kernels: each of them, moved into a function or a constructor, changed the kernels' register allocation
+// (tools/isa_diff.py), while these members and the two functions below leave the machine code as it was.  (The same
+// sensitivity is why some calls sit in one-line lambdas: a function called from a lambda is inlined when the lambda
+// is, late, as the lambda's own body was before; called from the kernel's text it is inlined before the optimiser runs.)
+template <int NW>
+struct MlpWave {
+  int r, wave, g, G;  // lane & 31; the wave in its workgroup; the workgroup's row group g of G
+  int64_t rows;
+  // a wave finishes 64 rows - two passes - per iteration
+  __device__ __forceinline__ int iters() const {
+    const int64_t nchunks = (rows + 63) >> 6;
+    return (int)((nchunks + (int64_t)G * NW - 1) / ((int64_t)G * NW));
+  }
+  // the 64-row chunk of passes 2 i, 2 i + 1
+  __device__ __forceinline__ int64_t chunk(int pass) const { return (int64_t)g * NW + wave + (int64_t)(pass >> 1) * G * NW; }
+  // the observation row lane r reads in this pass
+  __device__ __forceinline__ int64_t obs_row(int pass) const {
+    const int64_t row = chunk(pass) * 64 + 32 * (pass & 1) + r;
+    return row < rows ? row : rows - 1;  // (a ragged tail / an idle wave re-reads the last row; nothing is stored)
+  }
+};
+// The observation rows are read through a buffer descriptor over exactly the bytes the caller owns: the 16-wide
+// k-steps run past a row's end (into the next row: masked in the last k-step) and, for the last row, past the
+// array's end, where the hardware's range check returns zeros instead of touching memory.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mlp_obs_rsrc(const PolicyMlpArgs& A) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.obs), 0,
+                                           (int)(uint32_t)(((A.S.rows - 1) * A.ld_obs + A.k_in) * 4), 0x00020000);
 }
-#ifndef RVO3D_MLP_ABL
-#define RVO3D_MLP_ABL 0  // (timing experiments only: 1 no sampling, 8 no observation loads)
-#endif
-#ifndef RVO3D_MLP_XPREFETCH
-#define RVO3D_MLP_XPREFETCH 0  // 1: the next pass's rows are requested behind the last tile of layer 2
-#endif
+// Sparse rows.  The env writes an observation row as state_dim floats, then row_dim floats per kept velocity-obstacle
+// row, then zeros (in a rollout nearly every row has none or one: 21 of 102 floats); with the env's vo_count at hand a
+// wave knows how many leading 16-wide k-steps hold data for ANY of its 32 rows: the others are neither loaded nor
+// multiplied (a zero activation adds exactly nothing to a float32 sum; the last k-step always runs - it carries the
+// bias column).  KS1: no counts given, everything is loaded.
+template <int KS1, int NW>
+__device__ __forceinline__ int mlp_data_steps(const PolicyMlpArgs& A, const MlpWave<NW>& W, int pass) {
+  if (!A.cnt) return KS1;
+  int cn = A.cnt[W.obs_row(pass)];
+  cn = cn < 0 ? 0 : cn;  // (count 0 = the single all-zero row: no data behind the state)
+  const int mine = (A.state_dim + A.row_dim * cn + 15) >> 4;
+  int n = 1;
+#pragma unroll
+  for (int q = 1; q < KS1; ++q) n = __builtin_amdgcn_ballot_w64(mine > q) != 0 ? q + 1 : n;
+  return __builtin_amdgcn_readfirstlane(n);
+}
 #ifndef RVO3D_MLP_CLOCK
 #define RVO3D_MLP_CLOCK 0
 #endif
@@ -168,9 +207,8 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_kernel(const PolicyMlpArgs
   const unsigned char* const blob = A.blob + net * A.net_bytes;
   const unsigned char* const gw2 = blob + (int64_t)8 * KS1 * 1024;  // [8][16] blocks of 1 KB
   const int64_t rows = A.S.rows;
-  const int64_t nchunks = (rows + 63) >> 6;
-  const int iters = (int)((nchunks + (int64_t)G * NW - 1) / ((int64_t)G * NW));
-
+  const MlpWave<NW> W{r, wave, g, G, rows};
+  const int iters = W.iters();
   {  // the resident weights: the only workgroup-wide step of the kernel
     uint4* dst = reinterpret_cast<uint4*>(smem);
     const uint4* src = reinterpret_cast<const uint4*>(blob);
@@ -192,51 +230,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_kernel(const PolicyMlpArgs
   const float4 head_bias = *reinterpret_cast<const float4*>(blob + A.net_bytes - kMlpHeadBiasBytes);
   const SampleConsts SC = sample_consts(A.S);
 
-  // The observation rows are read through a buffer descriptor over exactly the bytes the caller owns: the 16-wide
-  // k-steps run past a row's end (into the next row: masked below) and, for the last row, past the array's end,
-  // where the hardware's range check returns zeros instead of touching memory.
-  const __amdgpu_buffer_rsrc_t obs_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(A.obs), 0, (int)(uint32_t)(((rows - 1) * A.ld_obs + A.k_in) * 4), 0x00020000);
-  f32x8 Xraw[KS1];
-  // Sparse rows.  The env writes an observation row as state_dim floats, then row_dim floats per kept velocity-obstacle
-  // row, then zeros (in a rollout nearly every row has none or one: 21 of 102 floats); with the env's vo_count at hand a
-  // wave knows how many leading 16-wide k-steps hold data for ANY of its 32 rows: the others are neither loaded nor
-  // multiplied (a zero activation adds exactly nothing to a float32 sum; the last k-step always runs - it carries the
-  // bias column).  n_data = KS1: no counts given, everything is loaded.
-  auto data_steps = [&](int pass) -> int {
-    if (!A.cnt) return KS1;
-    const int64_t c = (int64_t)g * NW + wave + (int64_t)(pass >> 1) * G * NW;
-    int64_t row = c * 64 + 32 * (pass & 1) + r;
-    if (row >= rows) row = rows - 1;
-    int cn = A.cnt[row];
-    cn = cn < 0 ? 0 : cn;  // (count 0 = the single all-zero row: no data behind the state)
-    const int mine = (A.state_dim + A.row_dim * cn + 15) >> 4;
-    int n = 1;
-#pragma unroll
-    for (int q = 1; q < KS1; ++q) n = __builtin_amdgcn_ballot_w64(mine > q) != 0 ? q + 1 : n;
-    return __builtin_amdgcn_readfirstlane(n);
-  };
-  auto request_rows = [&](int pass, int n_data) {
-#if !(RVO3D_MLP_ABL & 8)
-    const int64_t c = (int64_t)g * NW + wave + (int64_t)(pass >> 1) * G * NW;
-    int64_t row = c * 64 + 32 * (pass & 1) + r;
-    if (row >= rows) row = rows - 1;  // (a ragged tail / an idle wave re-reads the last row; nothing is stored)
-    const uint32_t off = (uint32_t)((row * A.ld_obs + 8 * h) * 4);
-#pragma unroll
-    for (int s = 0; s < KS1; ++s) {
-      if (s < n_data) {
-        const float4 lo = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(obs_rs, off + 64 * s, 0, 0));
-        const float4 hi = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(obs_rs, off + 64 * s + 16, 0, 0));
-        Xraw[s] = f32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-      } else {
-        Xraw[s] = f32x8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      }
-    }
-#endif
-  };
-#if RVO3D_MLP_XPREFETCH
-  request_rows(0, KS1);
-#endif
+  const __amdgpu_buffer_rsrc_t obs_rs = mlp_obs_rsrc(A);
 
   // Both layers are written as explicit software pipelines, one `sched_barrier` per MFMA: the A fragment of step
   // i + D is requested before the MFMA of step i, and the previous tile's epilogue (ReLU, conversion to the next
@@ -245,8 +239,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_kernel(const PolicyMlpArgs
   // optimiser defers all epilogues of a layer to its end, with every accumulator live.)
   // epilogue step q = 0..7 of a finished tile: registers 2 q, 2 q + 1 -> ReLU -> one packed bf16 pair
   auto epi = [&](const f32x16& acc, int q) -> uint32_t {
-    uint32_t w = __builtin_bit_cast(uint32_t, __builtin_convertvector(
-                                                  f32x2{relu_f32(acc[2 * q]), relu_f32(acc[2 * q + 1])}, bf16x2));
+    uint32_t w = pack_bf16x2(relu_f32(acc[2 * q]), relu_f32(acc[2 * q + 1]));
     asm volatile("" : "+v"(w));  // (pinned to this slot of the pipeline)
     return w;
   };
@@ -264,12 +257,23 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_kernel(const PolicyMlpArgs
 #pragma unroll 1
   for (int pass = 0; pass < 2 * iters; ++pass) {
     RVO3D_MLP_STAMP(3)
-#if !RVO3D_MLP_XPREFETCH
-    const int n_data = data_steps(pass);
-    request_rows(pass, n_data);
-#else
-    const int n_data = KS1;
-#endif
+    const int n_data = mlp_data_steps<KS1>(A, W, pass);
+    f32x8 Xraw[KS1];
+    // (a lambda on purpose: written straight into the pass, the same loads come out with another register allocation)
+    auto request_rows = [&]() {
+      const uint32_t off = (uint32_t)((W.obs_row(pass) * A.ld_obs + 8 * h) * 4);
+#pragma unroll
+      for (int s = 0; s < KS1; ++s) {
+        if (s < n_data) {
+          const float4 lo = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(obs_rs, off + 64 * s, 0, 0));
+          const float4 hi = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(obs_rs, off + 64 * s + 16, 0, 0));
+          Xraw[s] = f32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        } else {
+          Xraw[s] = f32x8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    };
+    request_rows();
     // ---- 32 observation rows as the B fragments of the first product (cast to bf16 on the way) ----
     bf16x8 X[KS1];
 #pragma unroll
@@ -341,16 +345,8 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_kernel(const PolicyMlpArgs
     f32x16 hd = {0};
     {
       constexpr int D2 = 4;
-      auto read_bias = [&](int m2) {
-        f32x16 b;
-        const float4* bp = reinterpret_cast<const float4*>(b2t + (m2 * 2 + h) * 16);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 v = bp[q];
-          b[4 * q] = v.x; b[4 * q + 1] = v.y; b[4 * q + 2] = v.z; b[4 * q + 3] = v.w;
-        }
-        return b;
-      };
+      // (wrapped in a lambda on purpose, as mlp_data_steps is in policy_mlp_x3_kernel: see MlpWave)
+      auto read_bias = [&](int m2) { return load_ctab(b2t, m2, h); };
       // per tile: first the NS streamed k-steps (their registers are then free for the next tile's request, which has
       // the TR resident steps to land), then the TR resident ones - one flat stream of 8 TR fragments in LDS, D2 in flight
       const unsigned char* const wb = w2r + lane * 16;
@@ -396,9 +392,6 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_kernel(const PolicyMlpArgs
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-#if RVO3D_MLP_XPREFETCH
-      if (pass + 1 < 2 * iters) request_rows(pass + 1, KS1);
-#endif
       // the last tile's epilogue and head products
       a3[0] = *reinterpret_cast<const bf16x8*>(w3l + 14 * 128);
       a3[1] = *reinterpret_cast<const bf16x8*>(w3l + 15 * 128);
@@ -417,14 +410,9 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_kernel(const PolicyMlpArgs
     }
     const float o0 = __shfl_xor(hd[0], 32, 64), o1 = __shfl_xor(hd[1], 32, 64), o2 = __shfl_xor(hd[2], 32, 64);
     const float z0 = (h ? o0 : zs0) + head_bias.x, z1 = (h ? o1 : zs1) + head_bias.y, z2 = (h ? o2 : zs2) + head_bias.z;
-    const int64_t c = (int64_t)g * NW + wave + (int64_t)(pass >> 1) * G * NW;
-    const int64_t row = c * 64 + lane;
+    const int64_t row = W.chunk(pass) * 64 + lane;
     if (row < rows) {
-#if RVO3D_MLP_ABL & 1
-      if (net == 0) A.S.logp[row] = z0 + z1 + z2;
-#else
       if (net == 0) finish_row(A.S, SC, row, z0, z1, z2);
-#endif
       else A.S.val[row] = z0;
     }
   }

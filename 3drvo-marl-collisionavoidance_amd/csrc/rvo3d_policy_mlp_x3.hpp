@@ -6,10 +6,12 @@
 // Reference: train/policy/policy_rnn_ac.py:57-69 (ac.step), :197-235 (GaussianActor), :238-257 (Critic), float32.
 // Part of the gfx950 device code (see rvo3d_device.hpp for the overview).
 //
-// Orientation, fragment maps and the permuted k order between layers are those of policy_mlp_kernel: weights are the
-// A operand, activations the B operand, a wave takes 32 batch rows per pass through all layers and finishes 64 rows
-// (one per lane) after two passes.  What changes is the weight and register budget ("The float32-class
-// policy step"): hi and lo double both.
+// Orientation, fragment maps and the permuted k order between layers (mfma_k_perm) are those of policy_mlp_kernel:
+// weights are the A operand, activations the B operand, a wave takes 32 batch rows per pass through all layers and
+// finishes 64 rows (one per lane) after two passes.  The pass -> row map, the observation descriptor and the count of
+// data k-steps are its functions (MlpWave, mlp_obs_rsrc, mlp_data_steps), the pack's decoding mlp_pack_elements; the
+// arithmetic of the split is rvo3d_mfma_tiles.hpp's.  What changes is the weight and register budget ("The
+// float32-class policy step"): hi and lo double both.
 //  * Registers: H1 as hi and lo fragments is 128 VGPRs; with two accumulators, the head tile, the split second-layer
 //    activations and two small weight rings the kernel stays at two waves per SIMD (256 registers) without spilling.
 //  * Weights: the hi halves of the second layer (128 KB), its bias table and the head rows (hi and lo) stay in LDS for
@@ -26,6 +28,7 @@
 
 #include <type_traits>
 
+#include "rvo3d_mfma_tiles.hpp"
 #include "rvo3d_policy_mlp.hpp"
 #include "rvo3d_rollout_kernels.hpp"
 
@@ -45,11 +48,6 @@ __host__ __device__ constexpr int64_t mlp_x3_net_bytes(int ks1) {
   return (int64_t)16 * 1024 * ks1 + kX3LdsBytes + kX3W2Bytes + kMlpHeadBiasBytes;
 }
 
-__device__ __forceinline__ void bf16_split(float v, uint16_t& hi, uint16_t& lo) {
-  hi = f32_to_bf16_rne(v);
-  lo = f32_to_bf16_rne(v - __builtin_bit_cast(float, (uint32_t)hi << 16));
-}
-
 __global__ void __launch_bounds__(256) mlp_x3_pack_kernel(const MlpPackArgs A) {
   const int net = blockIdx.y;
   const int ks1 = A.ks1;
@@ -60,71 +58,30 @@ __global__ void __launch_bounds__(256) mlp_x3_pack_kernel(const MlpPackArgs A) {
   uint16_t* const w3 = reinterpret_cast<uint16_t*>(blob + (int64_t)16 * 1024 * ks1 + kX3W2Bytes + kMlpB2Bytes);
   uint16_t* const w2l = reinterpret_cast<uint16_t*>(blob + (int64_t)16 * 1024 * ks1 + kX3LdsBytes);
   float* const hb = reinterpret_cast<float*>(blob + (int64_t)16 * 1024 * ks1 + kX3LdsBytes + kX3W2Bytes);
-  const int n_w1 = 8 * ks1 * 512, n_w2 = 8 * 16 * 512, n_b2 = 256, n_w3 = 16 * 4 * 2 * 8, n_hb = 4;
-  const int total = n_w1 + n_w2 + n_b2 + n_w3 + n_hb;
-  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-    int i = idx;
+  // every weight as hi and lo: W1 and W3 interleave them per k-step, W2 keeps two arrays; b2 and the head bias are float
+  mlp_pack_elements(A, net, [&](int section, int i, float v) RVO3D_INLINE {
+    if (section == kPackB2) { b2[i] = v; return; }
+    if (section == kPackHeadBias) { hb[i] = v; return; }
     uint16_t hi, lo;
-    if (i < n_w1) {  // W1[32 m + r][16 s + 8 h + j], the bias in column k_in
-      const int j = i & 7, lane = (i >> 3) & 63, ms = i >> 9, s = ms % ks1, m = ms / ks1;
-      const int row = 32 * m + (lane & 31), k = 16 * s + 8 * (lane >> 5) + j;
-      const float v = k < A.k_in ? A.w1[net][(int64_t)row * A.k_in + k] : (k == A.k_in ? A.b1[net][row] : 0.f);
-      bf16_split(v, hi, lo);
-      w1[(int64_t)ms * 1024 + (i & 511)] = hi;
-      w1[(int64_t)ms * 1024 + 512 + (i & 511)] = lo;
-      continue;
-    }
-    i -= n_w1;
-    if (i < n_w2) {  // W2[32 m2 + r][the unit the previous layer's fragment holds at (t, h, j)]
-      const int j = i & 7, lane = (i >> 3) & 63, t = (i >> 9) & 15, m2 = i >> 13;
-      const int row = 32 * m2 + (lane & 31), k = 32 * (t >> 1) + 16 * (t & 1) + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3);
-      bf16_split(A.w2[net][row * kMlpH + k], hi, lo);
+    bf16_split(v, hi, lo);
+    if (section == kPackW1) {         // [m][s][lane][j] -> [m][s][hi, lo][lane][j]
+      w1[(int64_t)(i >> 9) * 1024 + (i & 511)] = hi;
+      w1[(int64_t)(i >> 9) * 1024 + 512 + (i & 511)] = lo;
+    } else if (section == kPackW2) {
       w2h[i] = hi;
       w2l[i] = lo;
-      continue;
+    } else {                          // [t][row][h][j] -> [t][hi, lo][row][h][j]
+      w3[(i >> 6) * 128 + (i & 63)] = hi;
+      w3[(i >> 6) * 128 + 64 + (i & 63)] = lo;
     }
-    i -= n_w2;
-    if (i < n_b2) {  // [m2][h][reg]
-      const int reg = i & 15, h = (i >> 4) & 1, m2 = i >> 5;
-      b2[i] = A.b2[net][32 * m2 + mlp_acc_row(reg, h)];
-      continue;
-    }
-    i -= n_b2;
-    if (i < n_w3) {  // logical [t][row][h][j] -> [t][hi, lo][row][h][j]
-      const int j = i & 7, h = (i >> 3) & 1, tr = i >> 4, row = tr & 3, t = tr >> 2;
-      const int k = 32 * (t >> 1) + 16 * (t & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-      const int n_out = net == 0 ? 3 : 1;
-      bf16_split(row < n_out ? A.w3[net][row * kMlpH + k] : 0.f, hi, lo);
-      w3[t * 128 + (i & 63)] = hi;
-      w3[t * 128 + 64 + (i & 63)] = lo;
-      continue;
-    }
-    i -= n_w3;
-    hb[i] = i < (net == 0 ? 3 : 1) ? A.b3[net][i] : 0.f;
-  }
+  });
 }
 
 // relu, then the split of two accumulator registers into one packed hi pair and one packed lo pair
-struct X3Pair { uint32_t hi, lo; };
-__device__ __forceinline__ X3Pair relu_split2(float a, float b) {
-  const float x = relu_f32(a), y = relu_f32(b);
-  uint32_t hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x, y}, bf16x2));
-  const float xh = __builtin_bit_cast(float, hi << 16), yh = __builtin_bit_cast(float, hi & 0xffff0000u);
-  uint32_t lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x - xh, y - yh}, bf16x2));
-  asm volatile("" : "+v"(hi), "+v"(lo));  // (pinned to this slot of the pipeline)
-  return X3Pair{hi, lo};
-}
-__device__ __forceinline__ void split8(const f32x8& v, bf16x8& hi, bf16x8& lo) {
-  hi = __builtin_convertvector(v, bf16x8);
-  const f32x8 vh = __builtin_convertvector(hi, f32x8);
-  lo = __builtin_convertvector(v - vh, bf16x8);
-}
-// the three products of one k-step into acc
-__device__ __forceinline__ f32x16 mfma_x3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl,
-                                          const f32x16& c) {
-  f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+__device__ __forceinline__ Bf16x2Split relu_split2(float a, float b) {
+  Bf16x2Split p = split_bf16x2(relu_f32(a), relu_f32(b));
+  asm volatile("" : "+v"(p.hi), "+v"(p.lo));  // (pinned to this slot of the pipeline)
+  return p;
 }
 
 template <int KS1, int NW>
@@ -151,8 +108,8 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(blob_rs, lane * 16, off, 0));
   };
   const int64_t rows = A.S.rows;
-  const int64_t nchunks = (rows + 63) >> 6;
-  const int iters = (int)((nchunks + (int64_t)G * NW - 1) / ((int64_t)G * NW));
+  const MlpWave<NW> W{r, wave, g, G, rows};
+  const int iters = W.iters();
 
   {  // the resident weights: the only workgroup-wide step of the kernel
     uint4* dst = reinterpret_cast<uint4*>(smem);
@@ -163,25 +120,9 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
   const float4 head_bias = *reinterpret_cast<const float4*>(blob + A.net_bytes - kMlpHeadBiasBytes);
   const SampleConsts SC = sample_consts(A.S);
 
-  // observation rows through a buffer descriptor over exactly the caller's bytes (as policy_mlp_kernel)
-  const __amdgpu_buffer_rsrc_t obs_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(A.obs), 0, (int)(uint32_t)(((rows - 1) * A.ld_obs + A.k_in) * 4), 0x00020000);
-  auto row_of = [&](int pass) -> int64_t {
-    const int64_t c = (int64_t)g * NW + wave + (int64_t)(pass >> 1) * G * NW;
-    const int64_t row = c * 64 + 32 * (pass & 1) + r;
-    return row < rows ? row : rows - 1;  // (a ragged tail / an idle wave re-reads the last row; nothing is stored)
-  };
-  // leading 16-wide k-steps that hold data for any of the wave's 32 rows (KS1: no counts given)
-  auto data_steps = [&](int pass) -> int {
-    if (!A.cnt) return KS1;
-    int cn = A.cnt[row_of(pass)];
-    cn = cn < 0 ? 0 : cn;
-    const int mine = (A.state_dim + A.row_dim * cn + 15) >> 4;
-    int n = 1;
-#pragma unroll
-    for (int q = 1; q < KS1; ++q) n = __builtin_amdgcn_ballot_w64(mine > q) != 0 ? q + 1 : n;
-    return __builtin_amdgcn_readfirstlane(n);
-  };
+  const __amdgpu_buffer_rsrc_t obs_rs = mlp_obs_rsrc(A);
+  // (wrapped in a lambda on purpose: called straight from the pass, the function changes the register allocation)
+  auto data_steps = [&](int pass) -> int { return mlp_data_steps<KS1>(A, W, pass); };
 
   float zs0 = 0.f, zs1 = 0.f, zs2 = 0.f;
 #pragma unroll 1
@@ -190,7 +131,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
     // ---- 32 observation rows as the hi / lo B fragments of the first product ----
     bf16x8 Xh[KS1], Xl[KS1];
     {
-      const uint32_t off = (uint32_t)((row_of(pass) * A.ld_obs + 8 * h) * 4);
+      const uint32_t off = (uint32_t)((W.obs_row(pass) * A.ld_obs + 8 * h) * 4);
 #pragma unroll
       for (int s = 0; s < KS1; ++s) {
         f32x8 v = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -241,7 +182,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
         if (!kOverlap && j == NSTEP - 1) {  // (wide dense pass: the tile's epilogue at once, one accumulator live)
 #pragma unroll
           for (int q = 0; q < 8; ++q) {
-            const X3Pair p = relu_split2(accs[m & 1][2 * q], accs[m & 1][2 * q + 1]);
+            const Bf16x2Split p = relu_split2(accs[m & 1][2 * q], accs[m & 1][2 * q + 1]);
             H1h[2 * m + (q >> 2)][q & 3] = p.hi;
             H1l[2 * m + (q >> 2)][q & 3] = p.lo;
           }
@@ -249,7 +190,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
         if (kOverlap && m > 0) {  // the previous tile's epilogue: 8 steps over NSTEP k-steps
 #pragma unroll
           for (int q = (8 * j) / NSTEP; q < (8 * (j + 1)) / NSTEP; ++q) {
-            const X3Pair p = relu_split2(accs[(m - 1) & 1][2 * q], accs[(m - 1) & 1][2 * q + 1]);
+            const Bf16x2Split p = relu_split2(accs[(m - 1) & 1][2 * q], accs[(m - 1) & 1][2 * q + 1]);
             H1h[2 * (m - 1) + (q >> 2)][q & 3] = p.hi;
             H1l[2 * (m - 1) + (q >> 2)][q & 3] = p.lo;
           }
@@ -258,7 +199,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
       }
 #pragma unroll
       for (int q = 0; q < 8 * kOverlap; ++q) {
-        const X3Pair p = relu_split2(accs[1][2 * q], accs[1][2 * q + 1]);
+        const Bf16x2Split p = relu_split2(accs[1][2 * q], accs[1][2 * q + 1]);
         H1h[14 + (q >> 2)][q & 3] = p.hi;
         H1l[14 + (q >> 2)][q & 3] = p.lo;
       }
@@ -272,16 +213,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
     f32x16 hd = {0};
     {
       constexpr int D2 = 2;  // hi fragments in flight (LDS)
-      auto read_bias = [&](int m2) {
-        f32x16 b;
-        const float4* bp = reinterpret_cast<const float4*>(b2t + (m2 * 2 + h) * 16);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 v = bp[q];
-          b[4 * q] = v.x; b[4 * q + 1] = v.y; b[4 * q + 2] = v.z; b[4 * q + 3] = v.w;
-        }
-        return b;
-      };
+      auto read_bias = [&](int m2) { return load_ctab(b2t, m2, h); };  // (a lambda on purpose, as data_steps)
       const unsigned char* const wb = w2s + lane * 16;
       auto w2hi = [&](int i) { return *reinterpret_cast<const bf16x8*>(wb + i * 1024); };
       bf16x8 hring[D2];
@@ -308,7 +240,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
           cur = mfma_x3(ah, al, __builtin_bit_cast(bf16x8, H1h[t]), __builtin_bit_cast(bf16x8, H1l[t]), cur);
           if (m2 > 0 && t >= 1 && t <= 8) {  // the previous tile's epilogue, one packed pair per k-step
             const int q = t - 1;
-            const X3Pair p = relu_split2(prev[2 * q], prev[2 * q + 1]);
+            const Bf16x2Split p = relu_split2(prev[2 * q], prev[2 * q + 1]);
             h2h[q >> 2][q & 3] = p.hi;
             h2l[q >> 2][q & 3] = p.lo;
           }
@@ -327,7 +259,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
       // the last tile's epilogue and head products
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const X3Pair p = relu_split2(accs[1][2 * q], accs[1][2 * q + 1]);
+        const Bf16x2Split p = relu_split2(accs[1][2 * q], accs[1][2 * q + 1]);
         h2h[q >> 2][q & 3] = p.hi;
         h2l[q >> 2][q & 3] = p.lo;
       }
@@ -346,8 +278,7 @@ __global__ void __launch_bounds__(64 * NW) policy_mlp_x3_kernel(const PolicyMlpA
     }
     const float o0 = __shfl_xor(hd[0], 32, 64), o1 = __shfl_xor(hd[1], 32, 64), o2 = __shfl_xor(hd[2], 32, 64);
     const float z0 = (h ? o0 : zs0) + head_bias.x, z1 = (h ? o1 : zs1) + head_bias.y, z2 = (h ? o2 : zs2) + head_bias.z;
-    const int64_t c = (int64_t)g * NW + wave + (int64_t)(pass >> 1) * G * NW;
-    const int64_t row = c * 64 + lane;
+    const int64_t row = W.chunk(pass) * 64 + lane;
     if (row < rows) {
       if (net == 0) finish_row(A.S, SC, row, z0, z1, z2);
       else A.S.val[row] = z0;

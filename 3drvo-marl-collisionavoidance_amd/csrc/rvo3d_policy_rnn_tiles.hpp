@@ -16,7 +16,7 @@
 // Orientation (as rvo3d_policy_mlp.hpp).  Every product is computed TRANSPOSED - weights are the A operand, the tile's
 // 32 rows the B operand's columns -, so a 32 x 32 result tile holds the batch row on the lane and 16 hidden units in
 // the accumulator registers (unit 8 (i >> 2) + 4 h + (i & 3) of register i, lane half h).  The next product sums over
-// those units: the converted accumulators ARE its B fragments, in the permuted k order rnn_perm(); the packed weights of
+// those units: the converted accumulators ARE its B fragments, in the permuted k order mfma_k_perm(); the packed weights of
 // every product that reads hidden units (W_hh, the hidden part of W1, W2, W3) are stored in that order.  So the GRU's
 // hidden state, the features and both hidden layers never leave the registers: no LDS traffic between products.
 //
@@ -38,7 +38,8 @@
 #include <type_traits>
 #include <utility>
 
-#include "rvo3d_policy_mlp.hpp"
+#include "rvo3d_mfma_tiles.hpp"
+#include "rvo3d_rollout_kernels.hpp"
 
 namespace rvo3d {
 
@@ -47,12 +48,6 @@ constexpr int kRnnTilesWaves = 4;         // waves per workgroup (independent: o
 constexpr int kRnnTilesWorkHeader = 32;   // int32 cursors (count 1..slots) before the sub-lists
 constexpr int32_t kRnnTilesMagic = 0x524e5431;
 constexpr int kRnnTilesHeadBytes = 64;
-
-// k index (within the 32-unit group pair) of element j of lane half h in k-step t: the unit the accumulator of the
-// previous product holds there (see mlp_acc_row)
-__host__ __device__ constexpr int rnn_perm(int t, int h, int j) {
-  return 32 * (t >> 1) + 16 * (t & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-}
 
 // byte offsets inside the blob (every section 16-byte aligned; one fragment = 64 lanes x 8 bf16 = 1 KB)
 struct RnnTilesLayout {
@@ -103,9 +98,10 @@ __global__ void __launch_bounds__(256) rnn_tiles_pack_kernel(const RnnTilesPackA
   // a split fragment: element i of the logical [..][lane][8] array at 1 KB blocks 2 f (hi = bf16(v)) and 2 f + 1 (lo)
   auto split = [&](int64_t off, int64_t i, float v) {
     const int64_t at = ((i >> 9) << 10) + (i & 511);
-    const uint16_t hi = f32_to_bf16_rne(v);
+    uint16_t hi, lo;
+    bf16_split(v, hi, lo);
     reinterpret_cast<uint16_t*>(b + off)[at] = hi;
-    reinterpret_cast<uint16_t*>(b + off)[at + 512] = f32_to_bf16_rne(v - __builtin_bit_cast(float, (uint32_t)hi << 16));
+    reinterpret_cast<uint16_t*>(b + off)[at + 512] = lo;
   };
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -125,7 +121,7 @@ __global__ void __launch_bounds__(256) rnn_tiles_pack_kernel(const RnnTilesPackA
     for (int64_t i = t0; i < (int64_t)3 * HT * KH * 512; i += stride) {
       const int j = i & 7, lane = (i >> 3) & 63, t = (int)((i >> 9) % KH), gm = (int)((i >> 9) / KH), g = gm / HT, m = gm % HT;
       const int u = g * H + 32 * m + (lane & 31);
-      split(L.whh[d], i, A.w_hh[d][(int64_t)u * H + rnn_perm(t, lane >> 5, j)]);
+      split(L.whh[d], i, A.w_hh[d][(int64_t)u * H + mfma_k_perm(t, lane >> 5, j)]);
     }
     for (int64_t i = t0; i < (int64_t)HT * 32; i += stride) {
       const int reg = i & 15, h = (i >> 4) & 1, m = (int)(i >> 5);
@@ -143,12 +139,12 @@ __global__ void __launch_bounds__(256) rnn_tiles_pack_kernel(const RnnTilesPackA
     for (int64_t i = t0; i < (int64_t)8 * KS1 * 512; i += stride) {  // W1: k-steps 0..KH-1 the hidden part, KH the state
       const int j = i & 7, lane = (i >> 3) & 63, s = (int)((i >> 9) % KS1), m = (int)((i >> 9) / KS1);
       const int row = 32 * m + (lane & 31), h = lane >> 5;
-      const int col = s < KH ? SD + rnn_perm(s, h, j) : (8 * h + j < SD ? 8 * h + j : -1);
+      const int col = s < KH ? SD + mfma_k_perm(s, h, j) : (8 * h + j < SD ? 8 * h + j : -1);
       bf(L.w1[n], i, col >= 0 ? A.w1[n][(int64_t)row * D + col] : 0.f);
     }
     for (int64_t i = t0; i < 8 * 16 * 512; i += stride) {
       const int j = i & 7, lane = (i >> 3) & 63, t = (int)((i >> 9) & 15), m = (int)(i >> 13);
-      bf(L.w2[n], i, A.w2[n][(32 * m + (lane & 31)) * 256 + rnn_perm(t, lane >> 5, j)]);
+      bf(L.w2[n], i, A.w2[n][(32 * m + (lane & 31)) * 256 + mfma_k_perm(t, lane >> 5, j)]);
     }
     for (int64_t i = t0; i < 8 * 32; i += stride) {
       const int reg = i & 15, h = (i >> 4) & 1, m = (int)(i >> 5), u = 32 * m + mlp_acc_row(reg, h);
@@ -157,7 +153,7 @@ __global__ void __launch_bounds__(256) rnn_tiles_pack_kernel(const RnnTilesPackA
     }
     for (int64_t i = t0; i < 16 * 512; i += stride) {
       const int j = i & 7, lane = (i >> 3) & 63, t = (int)(i >> 9), row = lane & 31;
-      bf(L.w3[n], i, row < n_out ? A.w3[n][row * 256 + rnn_perm(t, lane >> 5, j)] : 0.f);
+      bf(L.w3[n], i, row < n_out ? A.w3[n][row * 256 + mfma_k_perm(t, lane >> 5, j)] : 0.f);
     }
     if (t0 < 4) fl(L.hb[n], t0, t0 < n_out ? A.b3[n][t0] : 0.f);
   }
@@ -204,34 +200,11 @@ __global__ void __launch_bounds__(256) rnn_tiles_bucket_kernel(const RnnTilesArg
 
 __device__ __forceinline__ int64_t min_i64(int64_t a, int64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-// A load from the blob through a GLOBAL pointer: the blob's address passes an empty asm (see the kernel) and comes out a
-// generic one, whose flat loads the compiler can only wait for all together (vmcnt and lgkmcnt both to 0) - that would
-// drain the fragment pipeline at every MFMA.
-// (T: a clang vector type - HIP's float4 is a class whose copy constructor takes a generic reference: flat again)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-template <class T>
-__device__ __forceinline__ T ld_blob(const unsigned char* p) {
-  return *(const __attribute__((address_space(1))) T*)(p);
-}
-__device__ __forceinline__ f32x16 load_ctab(const unsigned char* p, int m, int h) {  // a [tile][h][16] float table
-  f32x4 q[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = ld_blob<f32x4>(p + (m * 2 + h) * 64 + 16 * k);
-  f32x16 v;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) v[k] = q[k >> 2][k & 3];
-  return v;
-}
-
 // One flat stream of N weight fragments (1 KB each, lane-linear) through the MFMAs of `body(i, a)`: fragment i + D is
 // requested before MFMA i, and a scheduling barrier per MFMA keeps the compiler from hoisting the whole stream (it
 // would, and spill).  off(i): the fragment's byte offset in the blob.  The stream is expanded at compile time (a pack
 // expansion, not a loop: a 408-step loop exceeds the unroller's budget, and a rolled loop would index the register
 // arrays - hidden state, fragments - dynamically, i.e. through scratch), so every index is a constant.
-#define RVO3D_INLINE __attribute__((always_inline))
 template <int D, int N, class Off, class Body, int... I>
 __device__ __forceinline__ void frag_stream_seq(const unsigned char* base, Off& off, Body& body,
                                                 std::integer_sequence<int, I...>) {
@@ -319,6 +292,8 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
           const int k = 8 * h + q;
           xv[q] = k < 9 ? xp[k < 9 ? k : 0] : 0.0f;
         }
+        // (split8's arithmetic, written element by element: with split8 itself this kernel's registers are allocated
+        // differently; the same holds for split_bf16x2 and the state fragments below)
         const bf16x8 X = __builtin_convertvector(xv, bf16x8);
         f32x8 xr;
 #pragma unroll
@@ -352,11 +327,7 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
         auto step = [&](auto rec_tag) RVO3D_INLINE {
           constexpr bool REC = decltype(rec_tag)::value;
           constexpr int PER = REC ? 6 + 6 * KH : 6;  // fragments per unit tile: (gate, k-step) x (hi, lo)
-          // every product is split bf16: a_hi b_hi + a_hi b_lo (with the hi fragment) + a_lo b_hi (with the lo one)
-          auto mma3 = [&](f32x16& acc, const bf16x8& a, int part, const bf16x8& bh, const bf16x8& bl) RVO3D_INLINE {
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bh, acc, 0, 0, 0);
-            if (part == 0) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc, 0, 0, 0);
-          };
+          // every product is split bf16, a fragment at a time (mfma_x3_part)
           frag_stream<kRnnTilesDepth, HT * PER>(
               base,
               [&](int i) RVO3D_INLINE -> int64_t {
@@ -368,18 +339,18 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
               [&](auto ic, const bf16x8& a) RVO3D_INLINE {
                 constexpr int i = decltype(ic)::value, m = i / PER, q = i % PER, part = q & 1;
                 if constexpr (q == 0) {
-                  ar = load_ctab(bt, m, h);
-                  az = load_ctab(bt, HT + m, h);
-                  an = load_ctab(bt, 2 * HT + m, h);
-                  ahn = load_ctab(blob + L.bhn[d], m, h);
+                  ar = load_ctab_global(bt, m, h);
+                  az = load_ctab_global(bt, HT + m, h);
+                  an = load_ctab_global(bt, 2 * HT + m, h);
+                  ahn = load_ctab_global(blob + L.bhn[d], m, h);
                 }
                 if constexpr (q < 6) {
                   constexpr int g = q >> 1;
-                  mma3(g == 0 ? ar : g == 1 ? az : an, a, part, X, XL);
+                  mfma_x3_part(g == 0 ? ar : g == 1 ? az : an, a, part, X, XL);
                 } else {
                   constexpr int f = (q - 6) >> 1, t = f / 3, g = f % 3;
-                  mma3(g == 0 ? ar : g == 1 ? az : ahn, a, part, __builtin_bit_cast(bf16x8, hf[t]),
-                       __builtin_bit_cast(bf16x8, hl[t]));
+                  mfma_x3_part(g == 0 ? ar : g == 1 ? az : ahn, a, part, __builtin_bit_cast(bf16x8, hf[t]),
+                               __builtin_bit_cast(bf16x8, hl[t]));
                 }
                 if constexpr (q == PER - 1) gates(m);
               });
@@ -444,7 +415,7 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
     u32x4 F[KS1];  // the features as the B fragments of the first layers
 #pragma unroll
     for (int m = 0; m < HT; ++m) {
-      const f32x16 g = load_ctab(blob + L.ln_hg, m, h), bb = load_ctab(blob + L.ln_hb, m, h);
+      const f32x16 g = load_ctab_global(blob + L.ln_hg, m, h), bb = load_ctab_global(blob + L.ln_hb, m, h);
 #pragma unroll
       for (int q = 0; q < 8; ++q)
         F[2 * m + (q >> 2)][q & 3] = pack_bf16x2((hs[m][2 * q] - mean) * rstd * g[2 * q] + bb[2 * q],
@@ -481,7 +452,7 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
           [&](auto ic, const bf16x8& a) RVO3D_INLINE {
             constexpr int i = decltype(ic)::value, m = i / KS1, s1 = i % KS1;
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, F[s1]),
-                                                          s1 == 0 ? load_ctab(blob + L.b1[net], m, h) : acc, 0, 0, 0);
+                                                          s1 == 0 ? load_ctab_global(blob + L.b1[net], m, h) : acc, 0, 0, 0);
             if constexpr (s1 == KS1 - 1) {
 #pragma unroll
               for (int q = 0; q < 8; ++q) H1[2 * m + (q >> 2)][q & 3] = pack_bf16x2(relu_f32(acc[2 * q]), relu_f32(acc[2 * q + 1]));
@@ -500,7 +471,7 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
             constexpr int i = decltype(ic)::value, m = i / 18, q = i % 18;
             if constexpr (q < 16) {
               acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, H1[q]),
-                                                            q == 0 ? load_ctab(blob + L.b2[net], m, h) : acc, 0, 0, 0);
+                                                            q == 0 ? load_ctab_global(blob + L.b2[net], m, h) : acc, 0, 0, 0);
               if constexpr (q == 15) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) h2[k >> 2][k & 3] = pack_bf16x2(relu_f32(acc[2 * k]), relu_f32(acc[2 * k + 1]));
