@@ -18,8 +18,16 @@ struct Lds {
   // d + k (mod N) is slot d + k; and the exact-stage request masks
   float* w[12];                                  // x y z r [FL] (stored twice); vx vy vz kd ax ay az prio [FS]
   unsigned long long* mask2;                     // [NW][T] (word-major, see mi()) bit j: run pair_eval(me, j)
+  // one-wave workgroups: stage X1's pair list (x1_queue) and the words its "keep" verdicts come back in
+  uint32_t* x1keep;                              // [64]
+  uint16_t* x1q;                                 // [kX1Queue] owner slot | offset bit << 6
   int T;
 };
+
+// Capacity of the pair list.  The one-wave layout is 8 984 B without it and 16 workgroups share a CU's 160 KiB
+// (10 240 B each): 256 B of keep words + 2 B x 384 = 10 008 B.  Three full trips of 128 pairs; the rows sweep of 64
+// drones on 50 x 50 x 10 has ~210 candidates per wave, its sweep A ~120.  A wave with more takes the per-lane loop.
+constexpr int kX1Queue = 384;
 
 // Floats per "doubled" fp32 array (x y z r).  A drone d reaches neighbour d + k, k <= N/2, at
 // slot d + k: one env per workgroup (NW > 1) stores its N slots followed by a second copy of
@@ -53,6 +61,8 @@ __device__ __forceinline__ Lds carve_lds(unsigned char* base, int T, int nm, int
   L.any_reset = reinterpret_cast<int*>(ws + 8 * (size_t)FS);
   L.far = L.any_reset + epb;
   L.any_old = L.far + epb;
+  L.x1keep = reinterpret_cast<uint32_t*>(L.any_old + 1);
+  L.x1q = reinterpret_cast<uint16_t*>(L.x1keep + 64);
   L.T = T;
   return L;
 }
@@ -60,7 +70,7 @@ __host__ __device__ inline size_t lds_bytes(int T, int nm, int epb, int N, int N
   (void)nm;
   return (size_t)T * 8 * 8 + (size_t)T * NW * 8 + (size_t)T * 4 +
          (size_t)f32_len_nw(T, N, epb, NW) * 16 + (size_t)f32_single_nw(N, epb, NW) * 32 +
-         (size_t)epb * 8 + 4 + 16;
+         (size_t)epb * 8 + 4 + 16 + (NW == 1 ? 64 * 4 + (size_t)kX1Queue * 2 : 0);
 }
 
 __device__ __forceinline__ Drone lds_drone(const Lds& L, int k) {

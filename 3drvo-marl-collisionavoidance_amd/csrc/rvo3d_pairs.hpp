@@ -393,6 +393,174 @@ template <> struct OffsetSet<4> {
   __device__ __forceinline__ int count() const { return __builtin_popcountll(lo) + __builtin_popcountll(hi); }
 };
 
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// One end of two candidate pairs as stage X1 reads it from the fp32 image (two pairs per trip in packed fp32).
+struct X1End { v2f x, y, z, r, vx, vy, vz, kd, prio; };
+// Stage X1's verdicts for the two pairs: request the exact stage for the owner (pi) / the neighbour (pj); somebody
+// possibly approaches (keep, ROWS: the pair stays in the word filed for the next sweep A).
+struct X1Bits { bool pi0, pj0, pi1, pj1, keep0, keep1; };
+
+// The arithmetic of stage X1 for two pairs (me -> o), straight-line fp32: possibly approaching / touching and the
+// conservative cone pre-filter, for both directions.  ta* = 4 a of "me", ao* = the neighbours' action.
+// ZERO: both ends are observed with action 0.  Then both directions see the same 2 w = 0 - (v_i + v_j): one w, one
+// w^2, one dot product (dp_j = -dp_i exactly) - the same bits as the general chain fed with zeros.
+template <bool TOUCH, bool ZERO>
+__device__ __forceinline__ X1Bits x1_pairs(const Params& P, bool far, const X1End& me, const X1End& o, v2f tax,
+                                           v2f tay, v2f taz, v2f aox, v2f aoy, v2f aoz) {
+  // booleans are combined bitwise on purpose (no branches)
+  const v2f dx = o.x - me.x, dy = o.y - me.y, dz = o.z - me.z;
+  const v2f d2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
+  const v2f rs = o.r + me.r;
+  const v2f rs2 = rs * rs;
+  const v2f tch = __builtin_elementwise_fma(rs2, (v2f){1.00001f, 1.00001f}, (v2f){P.band, P.band});
+  // possibly approaching, each direction (v.rel > -eps)
+  const v2f vi = __builtin_elementwise_fma(me.vz, dz, __builtin_elementwise_fma(me.vy, dy, me.vx * dx));
+  const v2f vj = __builtin_elementwise_fma(o.vz, dz, __builtin_elementwise_fma(o.vy, dy, o.vx * dx));
+  // cone pre-filter: |ab| cos(alpha + 2e-3), slack x1_k2 on its square
+  const v2f gap = d2 - rs2;  // d^2 - R^2
+  // raw v_sqrt_f32 (1 ulp): the filter's slack covers it
+  const v2f sq_ = {__builtin_amdgcn_sqrtf(__builtin_fmaxf(gap.x, 0.f)),
+                   __builtin_amdgcn_sqrtf(__builtin_fmaxf(gap.y, 0.f))};
+  // K <= 0: the second clause below is empty (its bound becomes 0)
+  const v2f Kr = (v2f){0.999998f, 0.999998f} * sq_ - (v2f){2.0e-3f, 2.0e-3f} * rs;
+  const v2f K = {__builtin_fmaxf(Kr.x, 0.f), __builtin_fmaxf(Kr.y, 0.f)};
+  const v2f K2 = K * K * (v2f){P.x1_k2, P.x1_k2};
+  const v2f hx = me.vx + o.vx, hy = me.vy + o.vy, hz = me.vz + o.vz;
+  // 2 w_i, w_i = 2 a_i - (v_i + v_j) / 2  (get_PAA with equal priorities)
+  const v2f wix = tax - hx, wiy = tay - hy, wiz = taz - hz;
+  const v2f dpi = __builtin_elementwise_fma(dz, wiz, __builtin_elementwise_fma(dy, wiy, dx * wix));
+  const v2f wi2 = __builtin_elementwise_fma(wiz, wiz, __builtin_elementwise_fma(wiy, wiy, wix * wix));
+  // seen from j: rel -> -rel, 2 w_j = 4 a_j - (v_i + v_j)
+  v2f dpj, wj2;
+  if (ZERO) {
+    dpj = -dpi;
+    wj2 = wi2;
+  } else {
+    const v2f four2 = {4.f, 4.f};
+    const v2f wjx = four2 * aox - hx, wjy = four2 * aoy - hy, wjz = four2 * aoz - hz;
+    dpj = -__builtin_elementwise_fma(dz, wjz, __builtin_elementwise_fma(dy, wjy, dx * wjx));
+    wj2 = __builtin_elementwise_fma(wjz, wjz, __builtin_elementwise_fma(wjy, wjy, wjx * wjx));
+  }
+  const v2f cs = (v2f){P.x1_cs2, P.x1_cs2} * d2;
+  // signed squares: s = dp |dp|.  Surely outside the cone: cos < -cs (s < -cs w2), or
+  // 0 <= cos < cos(alpha + delta) with slack (0 <= s < K^2 w2); one bound per sign of s
+  // and ONE comparison s < bound (a NaN compares false: the pair is kept).
+  const v2f si = dpi * __builtin_elementwise_abs(dpi), sj = dpj * __builtin_elementwise_abs(dpj);
+  const v2f ci = -(cs * wi2), cj = -(cs * wj2), ki = wi2 * K2, kj = wj2 * K2;
+  X1Bits b;
+#define RVO3D_X1_HALF(c, pi, pj, kp)                                                          \
+  {                                                                                           \
+    /* lane predicates, combined with & | ! (no short circuit: no branches; the               \
+       compiler keeps them as wave masks and combines them on the scalar unit) */             \
+    const bool touch = TOUCH & (d2.c <= tch.c);                                               \
+    const bool ai = vi.c > -me.kd.c, aj = vj.c < o.kd.c;                                      \
+    const bool filt = (gap.c >= P.x1_gap) & (o.prio.c == me.prio.c);                          \
+    const bool oi = si.c < (si.c < 0.f ? ci.c : ki.c);                                        \
+    const bool oj = sj.c < (sj.c < 0.f ? cj.c : kj.c);                                        \
+    pi = far | touch | (ai & !(filt & oi));                                                   \
+    pj = far | touch | (aj & !(filt & oj));                                                   \
+    kp = far | ai | aj;                                                                       \
+  }
+  RVO3D_X1_HALF(x, b.pi0, b.pj0, b.keep0)
+  RVO3D_X1_HALF(y, b.pi1, b.pj1, b.keep1)
+#undef RVO3D_X1_HALF
+  return b;
+}
+
+// Inclusive prefix sum over the 64 lanes of a wave (every lane takes part): four shifts inside the rows of 16, then
+// the row totals (row_bcast15 into rows 1 and 3, row_bcast31 into rows 2 and 3).
+__device__ __forceinline__ int wave_prefix_sum(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31
+  return v;
+}
+
+// Two entries of the pair list (x1_queue), decoded: owner slot s, offset bit kb, owner's drone index d, owner and
+// neighbour in the doubled arrays (oa = el 2N + d, ob = oa + offset: the second copy, no wrap), the neighbour's drone
+// index jd and slot j.  N: the ring size, a power of two.
+struct X1Idx {
+  int s0, s1, kb0, kb1, d0, d1, oa0, oa1, ob0, ob1, jd0, jd1, j0, j1;
+  __device__ __forceinline__ X1Idx(uint32_t e, int N) {
+    s0 = (int)(e & 63u); s1 = (int)((e >> 16) & 63u);
+    kb0 = (int)((e >> 6) & 31u); kb1 = (int)((e >> 22) & 31u);
+    d0 = s0 & (N - 1); d1 = s1 & (N - 1);
+    oa0 = 2 * s0 - d0; oa1 = 2 * s1 - d1;
+    ob0 = oa0 + kb0 + 1; ob1 = oa1 + kb1 + 1;
+    jd0 = (d0 + kb0 + 1) & (N - 1); jd1 = (d1 + kb1 + 1) & (N - 1);
+    j0 = s0 - d0 + jd0; j1 = s1 - d1 + jd1;
+  }
+};
+
+// Stage X1 of a one-wave workgroup on a wave-compacted pair list.  A lane's candidates are as many as its
+// neighbourhood is crowded (64 drones on 50 x 50 x 10: 2-3 on average, 8 for the busiest lane), and the per-lane
+// loop makes as many trips as the busiest lane needs, at about a third lane use.  Here the wave first files all its
+// candidates as one queue in LDS - 16-bit entries (owner slot | offset bit << 6, slots relative to the wave), at
+// prefix-sum positions - and then every lane takes TWO entries per trip, whoever owns them: both ends come from the
+// fp32 image, the arithmetic is x1_pairs in the owner's orientation, and the verdicts go back as LDS atomics - pi
+// into the owner's request mask, pj into the neighbour's, keep into the owner's word of L.x1keep (cleared by the
+// caller along with the request masks, read back by the owner behind the caller's barrier).  The requests are
+// idempotent ORs: the bits are those of the per-lane loop.
+// N is the ring size, a power of two (the compile-time kernels).  act0: the lane's env is observed with action 0.
+// Returns false - nothing done, the caller walks its own candidates - when the wave has more than kX1Queue
+// candidates (dense worlds) or an env that bypasses the filters (far); both uniform over the wave.
+template <bool ROWS, bool TOUCH>
+__device__ __forceinline__ bool x1_queue(const Params& P, const Lds& L, int lane, int N, bool active, bool far,
+                                         bool act0, uint32_t cand) {
+  typedef uint32_t __attribute__((may_alias)) u32a;
+  if (!active) cand = 0u;
+  const int c = __builtin_popcount(cand);
+  const int incl = wave_prefix_sum(c);
+  const int total = __builtin_amdgcn_readlane(incl, 63);
+  if (total > kX1Queue || __ballot(active && far) != 0ull) return false;
+  for (int pos = incl - c; cand; cand &= cand - 1u, ++pos)
+    L.x1q[pos] = (uint16_t)((uint32_t)lane | ((uint32_t)__builtin_ctz(cand) << 6));
+  __syncthreads();  // (one wave: the queue is complete)
+  // (wave-uniform: every env of the wave is observed with action 0 - the usual rows sweep of the auto-reset step)
+  const bool zero = ROWS && __ballot(active && !act0) == 0ull;
+  for (int base = 0; base < total; base += 128) {
+    const int i0 = base + 2 * lane;
+    const bool on0 = i0 < total, on1 = i0 + 1 < total;
+    // (entries past the end are whatever LDS holds: 6 + 5 bits index inside the arrays, the verdicts are dropped)
+    uint32_t e = *reinterpret_cast<const u32a*>(L.x1q + i0);
+    X1Bits b;
+    {
+      const X1Idx k(e, N);
+#define RVO3D_LD2(K, F) ((v2f){L.w[K][k.F##0], L.w[K][k.F##1]})
+      const X1End me = {RVO3D_LD2(WX, oa), RVO3D_LD2(WY, oa), RVO3D_LD2(WZ, oa), RVO3D_LD2(WR, oa), RVO3D_LD2(WVX, s),
+                        RVO3D_LD2(WVY, s), RVO3D_LD2(WVZ, s), RVO3D_LD2(WKD, s), RVO3D_LD2(WPRIO, s)};
+      const X1End o = {RVO3D_LD2(WX, ob), RVO3D_LD2(WY, ob), RVO3D_LD2(WZ, ob), RVO3D_LD2(WR, ob), RVO3D_LD2(WVX, j),
+                       RVO3D_LD2(WVY, j), RVO3D_LD2(WVZ, j), RVO3D_LD2(WKD, j), RVO3D_LD2(WPRIO, j)};
+      const v2f z2 = {0.f, 0.f};
+      if (zero) {
+        b = x1_pairs<TOUCH, true>(P, false, me, o, z2, z2, z2, z2, z2, z2);
+      } else {
+        const v2f four2 = {4.f, 4.f};
+        b = x1_pairs<TOUCH, false>(P, false, me, o, four2 * RVO3D_LD2(WAX, s), four2 * RVO3D_LD2(WAY, s),
+                                   four2 * RVO3D_LD2(WAZ, s), RVO3D_LD2(WAX, j), RVO3D_LD2(WAY, j), RVO3D_LD2(WAZ, j));
+      }
+#undef RVO3D_LD2
+    }
+    // (several envs per wave: the slots are decoded again for the verdicts rather than carried - ten registers -
+    // across the arithmetic; the entry made opaque, or the compiler carries them all the same)
+    if (N != 64) asm volatile("" : "+v"(e));
+    const X1Idx k(e, N);
+    if (b.pi0 & on0) atomicOr(&L.mask2[k.s0], 1ull << k.jd0);
+    if (b.pi1 & on1) atomicOr(&L.mask2[k.s1], 1ull << k.jd1);
+    if (b.pj0 & on0) atomicOr(&L.mask2[k.j0], 1ull << k.d0);
+    if (b.pj1 & on1) atomicOr(&L.mask2[k.j1], 1ull << k.d1);
+    if (ROWS) {
+      if (b.keep0 & on0) atomicOr(&L.x1keep[k.s0], 1u << k.kb0);
+      if (b.keep1 & on1) atomicOr(&L.x1keep[k.s1], 1u << k.kb1);
+    }
+  }
+  return true;
+}
+
 // Symmetric sweep: every unordered pair {i, j} of an env is examined once, by the
 // drone whose index d satisfies j = d + k (mod N), 1 <= k <= N/2.
 //   stage G  (packed fp32, all offsets): possibly in range;
@@ -402,10 +570,14 @@ template <> struct OffsetSet<4> {
 //   stage X2 (fp64, requested pairs only): pair_eval.
 // G and X1 only ever drop pairs that pair_eval would return "nothing" for.
 // NW = ceil(N / 64): words per request mask (64 drones) and per offset mask (32 offsets).
-template <int NW, bool ROWS, bool TOUCH, bool TRAIN, bool GSHARE = false>
+// zero_act: the action is 0 whatever the fp32 image holds (observe).  act0: the image of this lane's env holds
+// action 0 for everybody (the env reset somebody): a wave whose envs all do takes the cheaper X1 (x1_queue).
+// QUEUE (one-wave workgroups with a power-of-two ring): stage X1 runs on the wave's compacted pair list (x1_queue)
+// unless the wave has too many candidates for it.
+template <int NW, bool ROWS, bool TOUCH, bool TRAIN, bool GSHARE = false, bool QUEUE = false>
 __device__ __forceinline__ int sweep_env(const Params& P, const Lds& L, int lane, int el, int d,
                                          int g, bool active, const Drone& S, const double a[3],
-                                         bool zero_act, bool& flag, double& tmin,
+                                         bool zero_act, bool act0, bool& flag, double& tmin,
                                          bool& collision, uint32_t gw[NW], bool have_gw) {
   flag = false;
   tmin = __builtin_inf();
@@ -432,9 +604,24 @@ __device__ __forceinline__ int sweep_env(const Params& P, const Lds& L, int lane
   }
 #pragma unroll
   for (int w = 0; w < NW; ++w) L.mask2[mi<NW>(L, lane, w)] = 0ull;
+  if (QUEUE && ROWS) L.x1keep[lane] = 0u;
   __syncthreads();
   unsigned long long m2r = 0ull;  // NW == 1: my own requests stay in a register
-  if (active) {
+  bool queued = false;  // stage X1 was done on the wave's pair list (uniform over the wave)
+  if (QUEUE) {
+    static_assert(!QUEUE || NW == 1, "the pair list belongs to one wave");
+    const bool far = active && L.far[el] != 0;
+    if (active && !have_gw) {  // stage G first: the list is built from every lane's word
+      const int o0 = el * 2 * N + d;
+      uint32_t valid[NW];
+      valid_offsets<NW>(N, d, valid);
+      gw[0] = far ? valid[0]
+                  : (gate_word<false>(P, L, o0, 0, H, L.w[WX][o0], L.w[WY][o0], L.w[WZ][o0], L.w[WR][o0]) & valid[0]);
+    }
+    have_gw = true;
+    if (!RVO3D_ABLATED(64 | 128)) queued = x1_queue<ROWS, TOUCH>(P, L, lane, N, active, far, zero_act || act0, gw[0]);
+  }
+  if (active && !queued) {
     const int o0 = el * 2 * N + d, os0 = el * N + d;
     const float mex = L.w[WX][o0], mey = L.w[WY][o0], mez = L.w[WZ][o0];
     const float mvx = L.w[WVX][os0], mvy = L.w[WVY][os0], mvz = L.w[WVZ][os0];
@@ -455,15 +642,13 @@ __device__ __forceinline__ int sweep_env(const Params& P, const Lds& L, int lane
     // stage X1, two candidate pairs per trip in packed fp32 (a lane with an odd count repeats
     // its last candidate: the requests are idempotent ORs).  One loop walks a lane's whole
     // candidate set up to 128 offsets (OffsetSet): fewer, fuller trips than one loop per word.
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const v2f mex2 = {mex, mex}, mey2 = {mey, mey}, mez2 = {mez, mez}, mer2 = {mer, mer};
-    const v2f mvx2 = {mvx, mvx}, mvy2 = {mvy, mvy}, mvz2 = {mvz, mvz};
-    // (the cone filter below works with 2 w = 4 a - (v_i + v_j): every term of its comparisons is
+    const X1End me = {{mex, mex}, {mey, mey}, {mez, mez}, {mer, mer}, {mvx, mvx},
+                      {mvy, mvy}, {mvz, mvz}, {mkd, mkd}, {mprio, mprio}};
+    // (the cone filter works with 2 w = 4 a - (v_i + v_j): every term of its comparisons is
     // homogeneous of degree 2 in w and a factor 2 is exact in binary, so the decisions are those of
     // w = 2 a - (v_i + v_j) / 2 bit for bit, without the three halvings per trip)
     const v2f tax = {4.f * max_, 4.f * max_}, tay = {4.f * may, 4.f * may},
               taz = {4.f * maz, 4.f * maz};
-    const int fr = far ? 1 : 0;
 #ifndef RVO3D_X1_CW
 #define RVO3D_X1_CW 4
 #endif
@@ -494,80 +679,20 @@ __device__ __forceinline__ int sweep_env(const Params& P, const Lds& L, int lane
         if (jd1 >= N) jd1 -= N;
         const int ja = el * N + jd0, jb = el * N + jd1;  // slots in the single-copy arrays
 #define RVO3D_LD2(K, i0, i1) ((v2f){L.w[K][i0], L.w[K][i1]})
-        // straight-line fp32; booleans are combined bitwise on purpose (no branches)
-        const v2f dx = RVO3D_LD2(WX, oa, ob) - mex2, dy = RVO3D_LD2(WY, oa, ob) - mey2,
-                  dz = RVO3D_LD2(WZ, oa, ob) - mez2;
-        const v2f jvx = RVO3D_LD2(WVX, ja, jb), jvy = RVO3D_LD2(WVY, ja, jb),
-                  jvz = RVO3D_LD2(WVZ, ja, jb);
-        const v2f jr = RVO3D_LD2(WR, oa, ob), jkd = RVO3D_LD2(WKD, ja, jb),
-                  jprio = RVO3D_LD2(WPRIO, ja, jb);
+        const X1End o = {RVO3D_LD2(WX, oa, ob), RVO3D_LD2(WY, oa, ob), RVO3D_LD2(WZ, oa, ob),
+                         RVO3D_LD2(WR, oa, ob), RVO3D_LD2(WVX, ja, jb), RVO3D_LD2(WVY, ja, jb),
+                         RVO3D_LD2(WVZ, ja, jb), RVO3D_LD2(WKD, ja, jb), RVO3D_LD2(WPRIO, ja, jb)};
         const v2f z2 = {0.f, 0.f};
         const v2f ajx = zero_act ? z2 : RVO3D_LD2(WAX, ja, jb),
                   ajy = zero_act ? z2 : RVO3D_LD2(WAY, ja, jb),
                   ajz = zero_act ? z2 : RVO3D_LD2(WAZ, ja, jb);
 #undef RVO3D_LD2
-        const v2f d2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-        const v2f rs = jr + mer2;
-        const v2f rs2 = rs * rs;
-        const v2f tch = __builtin_elementwise_fma(rs2, (v2f){1.00001f, 1.00001f},
-                                                  (v2f){P.band, P.band});
-        // possibly approaching, each direction (v.rel > -eps)
-        const v2f vi = __builtin_elementwise_fma(
-            mvz2, dz, __builtin_elementwise_fma(mvy2, dy, mvx2 * dx));
-        const v2f vj = __builtin_elementwise_fma(
-            jvz, dz, __builtin_elementwise_fma(jvy, dy, jvx * dx));
-        // cone pre-filter: |ab| cos(alpha + 2e-3), slack x1_k2 on its square
-        const v2f gap = d2 - rs2;  // d^2 - R^2
-        // raw v_sqrt_f32 (1 ulp): the filter's slack covers it
-        const v2f sq_ = {__builtin_amdgcn_sqrtf(__builtin_fmaxf(gap.x, 0.f)),
-                         __builtin_amdgcn_sqrtf(__builtin_fmaxf(gap.y, 0.f))};
-        // K <= 0: the second clause below is empty (its bound becomes 0)
-        const v2f Kr = (v2f){0.999998f, 0.999998f} * sq_ - (v2f){2.0e-3f, 2.0e-3f} * rs;
-        const v2f K = {__builtin_fmaxf(Kr.x, 0.f), __builtin_fmaxf(Kr.y, 0.f)};
-        const v2f K2 = K * K * (v2f){P.x1_k2, P.x1_k2};
-        const v2f hx = mvx2 + jvx, hy = mvy2 + jvy, hz = mvz2 + jvz;
-        // 2 w_i, w_i = 2 a_i - (v_i + v_j) / 2  (get_PAA with equal priorities)
-        const v2f wix = tax - hx, wiy = tay - hy, wiz = taz - hz;
-        const v2f dpi = __builtin_elementwise_fma(
-            dz, wiz, __builtin_elementwise_fma(dy, wiy, dx * wix));
-        const v2f wi2 = __builtin_elementwise_fma(
-            wiz, wiz, __builtin_elementwise_fma(wiy, wiy, wix * wix));
-        // seen from j: rel -> -rel, 2 w_j = 4 a_j - (v_i + v_j)
-        const v2f four2 = {4.f, 4.f};
-        const v2f wjx = four2 * ajx - hx, wjy = four2 * ajy - hy, wjz = four2 * ajz - hz;
-        const v2f dpj = -__builtin_elementwise_fma(
-            dz, wjz, __builtin_elementwise_fma(dy, wjy, dx * wjx));
-        const v2f wj2 = __builtin_elementwise_fma(
-            wjz, wjz, __builtin_elementwise_fma(wjy, wjy, wjx * wjx));
-        const v2f cs = (v2f){P.x1_cs2, P.x1_cs2} * d2;
-        // signed squares: s = dp |dp|.  Surely outside the cone: cos < -cs (s < -cs w2), or
-        // 0 <= cos < cos(alpha + delta) with slack (0 <= s < K^2 w2); one bound per sign of s
-        // and ONE comparison s < bound (a NaN compares false: the pair is kept).
-        const v2f si = dpi * __builtin_elementwise_abs(dpi), sj = dpj * __builtin_elementwise_abs(dpj);
-        const v2f ci = -(cs * wi2), cj = -(cs * wj2), ki = wi2 * K2, kj = wj2 * K2;
-#define RVO3D_X1_HALF(c, jd, pi, pj)                                                          \
-        {                                                                                     \
-          /* lane predicates, combined with & | ! (no short circuit: no branches; the        \
-             compiler keeps them as wave masks and combines them on the scalar unit) */       \
-          const bool touch = TOUCH & (d2.c <= tch.c);                                         \
-          const bool ai = vi.c > -mkd, aj = vj.c < jkd.c;                                     \
-          const bool filt = (gap.c >= P.x1_gap) & (jprio.c == mprio);                         \
-          const bool oi = si.c < (si.c < 0.f ? ci.c : ki.c);                                  \
-          const bool oj = sj.c < (sj.c < 0.f ? cj.c : kj.c);                                  \
-          pi = far | touch | (ai & !(filt & oi));                                             \
-          pj = far | touch | (aj & !(filt & oj));                                             \
-          if (ROWS) keep.add(kbit, (int)(far | ai | aj));                                     \
+        const X1Bits xb = x1_pairs<TOUCH, false>(P, far, me, o, tax, tay, taz, ajx, ajy, ajz);
+        bool pi0 = xb.pi0, pj0 = xb.pj0, pi1 = xb.pi1, pj1 = xb.pj1;
+        if (ROWS) {
+          keep.add(kb0, (int)xb.keep0);
+          keep.add(kb1, (int)xb.keep1);
         }
-        bool pi0, pj0, pi1, pj1;
-        {
-          const int kbit = kb0;
-          RVO3D_X1_HALF(x, jd0, pi0, pj0)
-        }
-        {
-          const int kbit = kb1;
-          RVO3D_X1_HALF(y, jd1, pi1, pj1)
-        }
-#undef RVO3D_X1_HALF
         pi1 &= two; pj1 &= two;
         if (NW == 1) {
           m2r |= ((unsigned long long)pi0 << jd0) | ((unsigned long long)pi1 << jd1);
@@ -588,6 +713,7 @@ __device__ __forceinline__ int sweep_env(const Params& P, const Lds& L, int lane
   if (ROWS && !TOUCH) RVO3D_STAMP(12);
   if (!ROWS) RVO3D_STAMP(14);
   __syncthreads();
+  if (QUEUE && ROWS && queued && active) gw[0] = L.x1keep[lane];  // the word filed for the next sweep A
 #ifdef RVO3D_DIAG
   if (P.dbg && active && RVO3D_ABLATED(128)) {  // diagnostics build, bit 128 = count: X2 requests of this workgroup (sum, max per lane)
     int c = 0;

@@ -503,6 +503,8 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   constexpr bool LITE = (MODE == kStepAutoReset);
   // stage G shared between the lanes (gate_words_shared): workgroups of exactly 64 NW drones
   constexpr bool GSH = NW > 1 && NFIX == 64 * NW;
+  // stage X1 on the wave's compacted pair list (x1_queue): one-wave workgroups with a compile-time ring of 16 / 32 / 64
+  constexpr bool XQ = NW == 1 && NFIX != 0;
 
   // Register discipline: values are loaded right before the phase that needs them and
   // stored as soon as they are final, so that across the sweeps little more than the
@@ -622,7 +624,7 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
       dev = deviation(prev, cur, p);
       if (dev > max_dev) max_dev = dev;
     }
-    const int kept = sweep_env<NW, true, true, TRAIN, GSH>(P, L, tid, el, d, g, active, S, zero3, true, flag,
+    const int kept = sweep_env<NW, true, true, TRAIN, GSH, XQ>(P, L, tid, el, d, g, active, S, zero3, true, true, flag,
                                                tmin, collision, gw, false);
     if (active) {
       write_vo_rows(P, L, tid, lbase, g, S, kept);
@@ -647,7 +649,7 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
 
   RVO3D_STAMP(2);
   // ---- sweep A: ir_gym.rvo_reward_list_cal on the pre-move state (ir_gym.py:50-62)
-  sweep_env<NW, false, false, TRAIN, GSH>(P, L, tid, el, d, g, active && !RVO3D_ABLATED(1), S, az, false, flag,
+  sweep_env<NW, false, false, TRAIN, GSH, XQ>(P, L, tid, el, d, g, active && !RVO3D_ABLATED(1), S, az, false, false, flag,
                               tmin, collision, gw, have_gw);
   // ---- everything else about this drone arrives in ONE batch of loads now (none of the
   //      addresses depends on a loaded value), then: drone.dronestate on the pre-move state
@@ -791,8 +793,8 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   if (LITE) {
     if (collide_env<NW, TRAIN, GSH>(P, L, tid, el, d, active && !RVO3D_ABLATED(2), S, gw)) collision = true;
   } else {
-    kept = sweep_env<NW, true, true, TRAIN, GSH>(P, L, tid, el, d, g, active && !RVO3D_ABLATED(2), S, az, false,
-                                     flag, tmin, collision, gw, false);
+    kept = sweep_env<NW, true, true, TRAIN, GSH, XQ>(P, L, tid, el, d, g, active && !RVO3D_ABLATED(2), S, az, false,
+                                     false, flag, tmin, collision, gw, false);
   }
   bool do_reset = false;
   if (active) {
@@ -895,8 +897,8 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     }
     if (RVO3D_ABLATED(2)) have_gw2 = false;  // diagnostics: the collision sweep was skipped
     if (NW > 1 && two_phase_rows(P, row0, nrows, full_rows) && !RVO3D_ABLATED(16)) early_zero_blocks<NW>(P, L, tid, row0, nrows);
-    kept = sweep_env<NW, true, false, TRAIN, GSH>(P, L, tid, el, d, g, active && !RVO3D_ABLATED(4), S, aa,
-                                      false, flag, tmin, c2, gw, have_gw2);
+    kept = sweep_env<NW, true, false, TRAIN, GSH, XQ>(P, L, tid, el, d, g, active && !RVO3D_ABLATED(4), S, aa,
+                                      false, env_reset, flag, tmin, c2, gw, have_gw2);
   }
   RVO3D_STAMP(7);
   // kept rows first (their loads from the row scratch would otherwise queue behind the fill's
