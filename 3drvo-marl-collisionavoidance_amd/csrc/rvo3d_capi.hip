@@ -1023,6 +1023,34 @@ int rvo3d_rollout_account(int32_t E, int32_t N, const float* reward, const uint8
   RVO3D_API_END
 }
 
+int rvo3d_gae(const float* rew, const float* val, const uint8_t* cut, int64_t steps, int64_t envs, int64_t drones,
+              double gamma, double lam, float* adv, float* ret, void* stream) {
+  RVO3D_API_BEGIN
+  // (every check precedes the first HIP call: the argument checks run on a machine without a GPU)
+  if (!rew || !val || !cut || !adv || !ret) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (steps < 1 || envs < 1 || drones < 1) return fail(RVO3D_ERR_INVALID, "need steps >= 1, envs >= 1 and drones >= 1");
+  if (!std::isfinite(gamma) || !std::isfinite(lam)) return fail(RVO3D_ERR_INVALID, "gamma and lam must be finite");
+  // one lane per column in 256-lane workgroups on a 1-D grid; the byte ranges below stay far inside 64 bits
+  const int64_t kMaxColumns = (int64_t)0x7fffffff * 256, kMaxElems = (int64_t)1 << 58;
+  if (envs > kMaxColumns / drones || steps > kMaxElems / (envs * drones))
+    return fail(RVO3D_ERR_INVALID, "steps * envs * drones too large");
+  const uint64_t n4 = (uint64_t)steps * (uint64_t)envs * (uint64_t)drones * 4, n1 = (uint64_t)steps * (uint64_t)envs;
+  auto overlap = [](const void* a, uint64_t an, const void* b, uint64_t bn) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bn && y < x + an;
+  };
+  if (overlap(adv, n4, rew, n4) || overlap(adv, n4, val, n4) || overlap(adv, n4, cut, n1) ||
+      overlap(ret, n4, rew, n4) || overlap(ret, n4, val, n4) || overlap(ret, n4, cut, n1) || overlap(adv, n4, ret, n4))
+    return fail(RVO3D_ERR_INVALID, "adv / ret overlap an input or each other: the outputs need storage of their own");
+  const int64_t columns = envs * drones;
+  rvo3d::GaeArgs A{rew, val, cut, steps, envs, drones, gamma, gamma * lam, adv, ret};
+  hipLaunchKernelGGL(rvo3d::gae_kernel, dim3((unsigned)((columns + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
 int rvo3d_set_reward_f64(rvo3d_env* h, double* reward64) {
   RVO3D_API_BEGIN
   if (!h) return fail(RVO3D_ERR_INVALID, "null handle");

@@ -297,6 +297,72 @@ __global__ void __launch_bounds__(512) rollout_account_kernel(const AccountArgs 
   }
 }
 
+// ---- GAE of a finished rollout (multi_PPObuf.finish_path(0) + get, multi_ppo.py:68-91), one lane per column ----
+// Column c = e N + n of the [T][E][N] buffer: at every step a wave's lanes read consecutive addresses.  The recurrence
+// runs from t = T - 1 down in binary64, each operation rounded on its own (the library is built with -ffp-contract=off,
+// no fma here), exactly as lfilter runs discount_cumsum over the float64 arrays np.append makes:
+//     end = cut[t][e] != 0 || t == T - 1;   nv, na, nr = end ? 0 : (v, adv, ret)[t + 1]
+//     delta = (r[t] + gamma nv) - v[t];     adv[t] = delta + (gamma lam) na;     ret[t] = r[t] + gamma nr
+// The path end is a SELECT, not a product with 0: the reference keeps every path in an array of its own, so an inf / nan
+// reward stays inside its path (0 inf = nan would carry it into every earlier path of the column).
+// The loads of a step do not depend on the recurrence: the time loop runs in chunks of RVO3D_GAE_UNROLL steps, a chunk's
+// 3 U loads issued before its arithmetic (the compiler waits with a counted vmcnt per step).  The last chunk's missing
+// steps load row 0 again instead of branching around each load (a branch per load drains the queue every time).
+// 64-bit element offsets throughout: T E N 4 bytes pass 2^32 at shapes in use.
+struct GaeArgs {
+  const float* rew;    // [T][E][N]
+  const float* val;    // [T][E][N]
+  const uint8_t* cut;  // [T][E]  non-zero: the paths of the env end behind step t (row T - 1 is not looked at: always an end)
+  int64_t T, E, N;
+  double gamma, gamma_lam;  // gamma * lam: ONE double product, computed on the host as Python computes it
+  float* adv;          // [T][E][N]
+  float* ret;          // [T][E][N]
+};
+
+#ifndef RVO3D_GAE_UNROLL
+#define RVO3D_GAE_UNROLL 8   // measured against 2, 4 and 16 at 64 x 4096, T = 16 / 128: profiles/r07/gae.txt
+#endif
+
+__global__ void __launch_bounds__(256) gae_kernel(const GaeArgs A) {
+  constexpr int U = RVO3D_GAE_UNROLL;
+  const int64_t EN = A.E * A.N;
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= EN) return;
+  // (a wave spans two envs when N is no multiple of 64: the env, and with it the cut byte, is per lane)
+  const int64_t e = EN <= 0xffffffffLL ? (int64_t)((uint32_t)c / (uint32_t)A.N) : c / A.N;
+  const float* __restrict__ rew = A.rew + c;
+  const float* __restrict__ val = A.val + c;
+  const uint8_t* __restrict__ cut = A.cut + e;
+  float* __restrict__ adv = A.adv + c;
+  float* __restrict__ ret = A.ret + c;
+  double nv = 0.0, na = 0.0, nr = 0.0;
+  for (int64_t top = A.T - 1; top >= 0; top -= U) {
+    float r[U], v[U];
+    uint8_t k[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int64_t t = top - j >= 0 ? top - j : 0;
+      r[j] = rew[t * EN];
+      v[j] = val[t * EN];
+      k[j] = cut[t * A.E];
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int64_t t = top - j;
+      if (t < 0) break;
+      const bool end = k[j] != 0 || t == A.T - 1;
+      const double rd = (double)r[j], vd = (double)v[j];
+      const double bv = end ? 0.0 : nv, ba = end ? 0.0 : na, br = end ? 0.0 : nr;
+      const double delta = (rd + A.gamma * bv) - vd;
+      na = delta + A.gamma_lam * ba;
+      nr = rd + A.gamma * br;
+      nv = vd;
+      adv[t * EN] = (float)na;
+      ret[t * EN] = (float)nr;
+    }
+  }
+}
+
 // ---- rnn_Reader for one-step sequences (policy_rnn_ac.py:75-127: biGRU over the VO rows, sum of the two final hidden
 //      states, concat with the proprioceptive part, LayerNorm) ----
 // In a rollout nearly every drone has zero or one VO row, and a GRU over a one-step sequence from h = 0 is one cell

@@ -105,10 +105,41 @@ def gae_scan_loop(rew, val, cut, gamma=0.99, lam=0.97):
     return adv.to(torch.float32), ret.to(torch.float32)
 
 
-class RolloutBuffer:
-    """[T, E, N, ...] storage on the device (the batched multi_PPObuf, multi_ppo.py:39-94)."""
+def gae_device(rew, val, cut, gamma=0.99, lam=0.97):
+    """The same scan as ONE HIP launch (rvo3d_gae): the step-by-step recurrence of `gae_scan_loop` in float64, one lane
+    per column, no temporaries.  rew, val: contiguous float32 CUDA tensors [T, E, N]; cut: [T, E] torch.bool or
+    torch.uint8 on the same device (any non-zero byte ends the env's paths behind step t; a bool tensor's storage is
+    passed as it is).  Returns (adv, ret) float32 [T, E, N], on torch's current stream of that device.
+    Unlike the two scans above the path end is a select, not a product with 0: the result is multi_PPObuf's to the last
+    bit, and an inf / nan reward stays inside its own path."""
+    import ctypes as C
+    from .. import _lib
+    for name, x in (("rew", rew), ("val", val)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3:
+            raise ValueError(f"{name} must be a float32 tensor [T, E, N]")
+    if not isinstance(cut, torch.Tensor) or cut.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("cut must be a torch.bool or torch.uint8 tensor [T, E]")
+    T, E, N = rew.shape
+    if min(T, E, N) < 1 or val.shape != rew.shape or tuple(cut.shape) != (T, E):
+        raise ValueError(f"need rew, val [T, E, N] with T, E, N >= 1 and cut [T, E]; got {tuple(rew.shape)}, "
+                         f"{tuple(val.shape)}, {tuple(cut.shape)}")
+    if not rew.is_cuda or val.device != rew.device or cut.device != rew.device:
+        raise ValueError("rew, val and cut must be on one CUDA device")
+    if not (rew.is_contiguous() and val.is_contiguous() and cut.is_contiguous()):
+        raise ValueError("rew, val and cut must be contiguous")
+    adv, ret = torch.empty_like(rew), torch.empty_like(rew)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(rew.device):
+        _lib.check(_lib.lib().rvo3d_gae(p(rew), p(val), p(cut), T, E, N, float(gamma), float(lam), p(adv), p(ret),
+                                        C.c_void_p(torch.cuda.current_stream(rew.device).cuda_stream)), "rvo3d_gae")
+    return adv, ret
 
-    def __init__(self, T, E, N, obs_width, act_dim, device, gamma=0.99, lam=0.95):
+
+class RolloutBuffer:
+    """[T, E, N, ...] storage on the device (the batched multi_PPObuf, multi_ppo.py:39-94).  fused_gae=True: get()
+    computes the advantages with `gae_device` (one HIP launch) where the buffer is on a GPU; a CPU buffer ignores it."""
+
+    def __init__(self, T, E, N, obs_width, act_dim, device, gamma=0.99, lam=0.95, fused_gae=False):
         f32 = dict(dtype=torch.float32, device=device)
         # T + 1 observation slots: slot t is what the policy saw at step t; the env writes the
         # observation after step t straight into slot t + 1 (no copies in the rollout loop)
@@ -120,6 +151,7 @@ class RolloutBuffer:
         self.logp = torch.zeros((T, E, N), **f32)
         self.cut = torch.zeros((T, E), dtype=torch.bool, device=device)
         self.gamma, self.lam, self.ptr, self.T = gamma, lam, 0, T
+        self.fused_gae = bool(fused_gae)
 
     def store(self, obs, cnt, act, rew, val, logp):
         assert self.ptr < self.T  # multi_ppo.py:59
@@ -136,8 +168,11 @@ class RolloutBuffer:
 
     def get(self):
         assert self.ptr == self.T  # buffer has to be full (multi_ppo.py:80)
-        cut = self.cut.unsqueeze(-1).expand_as(self.rew)
-        adv, ret = gae_scan(self.rew, self.val, cut, self.gamma, self.lam)
+        if self.fused_gae and self.rew.is_cuda:
+            adv, ret = gae_device(self.rew, self.val, self.cut, self.gamma, self.lam)
+        else:
+            cut = self.cut.unsqueeze(-1).expand_as(self.rew)
+            adv, ret = gae_scan(self.rew, self.val, cut, self.gamma, self.lam)
         self.ptr = 0
         self.cut.zero_()
         flat = lambda x: x.reshape((-1,) + x.shape[3:])
@@ -156,7 +191,7 @@ class multi_ppo:
                  max_update_num=None, mpi=False, figure_save_path=None, minibatch_size=None,
                  dist=None, sanitize_rewards=True, amp=False, reference_order=False, fused_rollout=True,
                  tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False,
-                 fused_rnn_tiles=False, **kwargs):
+                 fused_rnn_tiles=False, fused_gae=False, **kwargs):
         np.random.seed(seed)
         self.env, self.ac, self.dist = env, ac_policy, dist
         # The agent order of the reference-order update comes from a generator of its own, seeded like
@@ -186,6 +221,11 @@ class multi_ppo:
                 raise ValueError("fused_rnn_tiles=True needs an rnn_ac with a shared GRU / biGRU reader of hidden 64 or "
                                  "256, in_dim 9, state_dim <= 16, (256, 256) ReLU heads, on a GPU, and 1..12 VO slots")
         self.fused_rnn_tiles = bool(fused_rnn_tiles)
+        # the advantages of RolloutBuffer.get() from ONE HIP launch (rvo3d_gae: the reference's recurrence, bit for bit,
+        # no temporaries) instead of gae_scan's ~30 float64 tensor ops; any rollout mode, both update modes; a CPU
+        # buffer ignores it.  Opt-in: advantages / returns differ from gae_scan's by a few float32 ulps, so switching
+        # it on changes the default results - flipping the default is a later decision
+        self.fused_gae = bool(fused_gae)
         # the fast paths' per-step launches replayed as HIP graphs from the second rollout on (see _collect_fused);
         # opt-in: measured at 64 x 4096, 0.158 ms per step with and 0.157-0.161 without - the gaps between the dependent
         # kernels of a graph are what they are between stream launches.  Across update(): the "mlp" graphs survive an
@@ -238,7 +278,8 @@ class multi_ppo:
         # amp=True runs the policy GEMMs of the rollout in bf16 (MFMA); the reference is fp32
         self.amp = amp
         self.nonfinite_rewards = 0
-        self.buf = RolloutBuffer(steps_per_epoch, self.E, self.N, env.W, 3, self.device, gamma, lam)
+        self.buf = RolloutBuffer(steps_per_epoch, self.E, self.N, env.W, 3, self.device, gamma, lam,
+                                 fused_gae=self.fused_gae)
         self.ep_len = torch.zeros((self.E, self.N), dtype=torch.int32, device=self.device)
         self.ep_ret = torch.zeros((self.E, self.N), dtype=torch.float32, device=self.device)
         self.log = []

@@ -334,6 +334,22 @@ int rvo3d_rollout_account(int32_t num_envs, int32_t num_drones, const float *rew
                           float *rew_slot, float *ep_ret, int32_t *ep_len, uint8_t *cut_slot,
                           uint8_t *extra_mask, double *sums, int32_t *any_extra, void *stream);
 
+/* multi_PPObuf.finish_path(0) + get (train/policy/multi_ppo.py:68-91) for every column of a [T][E][N] rollout in ONE
+ * launch: rew / val / adv / ret [steps][envs][drones] float32, cut [steps][envs] bytes (any non-zero byte: the paths of
+ * that env end behind step t - what rvo3d_rollout_account writes; a torch.bool storage serves as it is).  Per column,
+ * from t = steps - 1 down, in float64 (np.append promotes the reference's float32 buffers), every operation rounded on
+ * its own as lfilter runs discount_cumsum:
+ *     delta = (r[t] + gamma * V[t+1]) - V[t];  adv[t] = delta + (gamma * lam) * adv[t+1];  ret[t] = r[t] + gamma * ret[t+1]
+ * with V / adv / ret[t+1] taken as 0 behind a path end; results are stored as float32 (round to nearest even).  The
+ * path end is a SELECT, not a multiplication by 0: as in the reference, where every path is an array of its own, an
+ * inf / nan reward (sanitize off) makes the steps of its own path before it non-finite and no other.  The byte of row
+ * steps - 1 is ignored: the end of the buffer ends every path.  gamma, lam finite; bootstrap value 0 only (the
+ * reference's trainer passes no other).  adv and ret must not overlap rew, val, cut or each other (checked:
+ * RVO3D_ERR_INVALID).  No handle: plain device pointers of the current device, enqueued on `stream`; every argument
+ * check runs before the first HIP call. */
+int rvo3d_gae(const float *rew, const float *val, const uint8_t *cut, int64_t steps, int64_t envs, int64_t drones,
+              double gamma, double lam, float *adv, float *ret, void *stream);
+
 /* mdin.drone_step returns its rewards as Python floats (mdin.py:28: rvo_reward + mov_reward in
  * float64).  Attach a device buffer reward64 [E][N] and every following step (all three step
  * entry points) also writes the float64 value next to the float32 one; NULL detaches.  The

@@ -21,7 +21,7 @@ for t in range(600):
     env.step(acts[t % 16], autoreset=True)
 
 
-def timed(name, fn, bytes_per_drone=None):
+def timed(name, fn, bytes_per_drone=None, per_drone=True):
     for _ in range(5):
         fn(0)
     torch.cuda.synchronize()
@@ -32,7 +32,9 @@ def timed(name, fn, bytes_per_drone=None):
     ts = np.asarray([a.elapsed_time(b) for a, b in ev])
     us = float(ts[ts <= 3 * np.median(ts)].mean()) * 1e3  # (without host-stall samples, see bench.py)
     extra = "" if bytes_per_drone is None else "  %.0f GB/s of its %d algorithmic bytes per drone" % (E * N * bytes_per_drone / us / 1e3, bytes_per_drone)
-    print("%-44s %8.1f us  %.3e drones/s%s" % (name, us, E * N / (us * 1e-6), extra), flush=True)
+    rate = "  %.3e drones/s%s" % (E * N / (us * 1e-6), extra) if per_drone else ""  # (no per-drone rate for a T-step scan)
+    print("%-44s %8.1f us%s" % (name, us, rate), flush=True)
+    return us
 
 
 W = env.W
@@ -54,3 +56,24 @@ timed("des_vel (cal_des_list)", lambda i: env.des_vel(), 48 + 24)
 timed("rvo_vel (classical RVO velocity selection)", lambda i: env.rvo_vel(vmax=(2.0, 2.0, 2.0), acceler=0.5))
 flags = env.error_flags()
 print("device error word", flags)
+
+# GAE of a finished [T, E, N] rollout: the default scan (gae_scan, ~30 float64 tensor ops) and the one-launch kernel
+# (gae_device -> rvo3d_gae), on random data with cuts at density 0.05; GB/s over the kernel's algorithmic bytes (one
+# read of rew and val, one write of adv and ret, the cut bytes); transient memory = peak allocation above the inputs (adv and ret included)
+from rvo3d_amd.policy import gae_device, gae_scan
+for T in (16, 128):
+    g = torch.Generator(device="cuda").manual_seed(T)
+    rew = torch.randn((T, E, N), device="cuda", generator=g) * 3
+    val = torch.randn((T, E, N), device="cuda", generator=g) * 2
+    cut = torch.rand((T, E), device="cuda", generator=g) < 0.05
+    cut3 = cut.unsqueeze(-1).expand_as(rew)  # (as RolloutBuffer.get() passes it)
+    nbytes = 16 * T * E * N + T * E
+    for name, fn in (("gae_scan", lambda i: gae_scan(rew, val, cut3, 0.99, 0.97)),
+                     ("gae_device", lambda i: gae_device(rew, val, cut, 0.99, 0.97))):
+        torch.cuda.synchronize(); torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        us = timed("%s T = %d" % (name, T), fn, per_drone=False)
+        print("    %-40s %8.1f GB/s of its %d algorithmic bytes; transient memory %.1f MB" % (
+            "", nbytes / us / 1e3, nbytes, (torch.cuda.max_memory_allocated() - base) / 1e6), flush=True)
+    del rew, val, cut, cut3
