@@ -3,7 +3,9 @@
 // exceptions across the boundary, no allocation in step/observe.
 #include "../../include/rvo3d.h"
 #include "rvo3d_device.hpp"
+#include "rvo3d_host_setup.hpp"
 
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -47,20 +49,9 @@ int api_caught(const char* what) noexcept {
   catch (const std::exception& e) { return api_caught(e.what()); } \
   catch (...) { return api_caught("unknown"); }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-// x ** 2 as the reference computes it: glibc pow (the volatile exponent keeps
-// the compiler from folding the call into x * x).
-volatile double kTwo = 2.0;
-inline double py_sq(double x) { return std::pow(x, kTwo); }
-
-// max{x : sqrt(x) <= tau} for the host's correctly rounded sqrt: `norm <= tau`
-// in the reference is exactly `norm^2 <= sq_threshold(tau)` on the device.
-double sq_threshold(double tau) {
-  volatile double x = tau * tau;
-  while (std::sqrt(std::nextafter((double)x, INFINITY)) <= tau) x = std::nextafter((double)x, INFINITY);
-  while (std::sqrt((double)x) > tau) x = std::nextafter((double)x, -INFINITY);
-  return x;
-}
+using rvo3d::align_up;
+using rvo3d::Pick;
+using rvo3d::pick_kernel;
 }  // namespace
 
 struct rvo3d_env {
@@ -72,7 +63,7 @@ struct rvo3d_env {
   bool world_loaded = false;
   bool dv_valid = false;  // dvk_a/dvk_b describe the current state (see Params::dv_cached)
   bool g_valid = false;   // gcache describes the current state (see Params::g_cached)
-  int threads = 0, blocks = 0, lds = 0;
+  rvo3d::Geometry geo{};  // threads, blocks, LDS bytes of the step's launch
 };
 
 namespace {
@@ -138,30 +129,9 @@ int check(rvo3d_env* h, bool need_world, DeviceGuard& g) {
   return g.enter(h->cfg.device);
 }
 
-// The compile-time-N instantiation (NFIX) a handle's shape selects, 0 = the generic kernel of its NW.
-// One place decides it: launch_nw() launches it and rvo3d_kernel_name() reports it.
-// Which instantiation a handle's shape runs on: the compile-time ring size NFIX (0 = the generic kernel of
-// its NW) and whether N is smaller than it (padded: ghost lanes).  One place decides; launch_nw() launches
-// it and rvo3d_kernel_name() reports it.
-struct Pick { int nfix; bool pad; };
-Pick pick_kernel(const Params& P) {
-  if (P.nw == 1) {
-    // a one-wave workgroup of epb envs: segments of 64 / epb lanes
-    const int seg = (P.epb == 1 || P.epb == 2 || P.epb == 4) ? 64 / P.epb : 0;
-    if (seg && P.N == seg) return {seg, false};
-    if (seg >= 32 && P.N < seg) return {seg, true};  // 33..63 drones on the 64 kernel, 22..31 on the 32 one
-    return {0, false};
-  }
-  // multi-wave workgroups: the compile-time kernels take any N up to their size
-  if (P.nw == 2) return {128, true};
-  if (P.nw == 3) return {192, true};
-  if (P.nw == 4) return {256, true};
-  return {0, false};
-}
-
 template <int MODE, int NW, int NFIX, bool TRAIN, bool PAD>
 void launch_inst(rvo3d_env* h, const Params& P, hipStream_t s) {
-  hipLaunchKernelGGL((rvo3d::env_kernel<MODE, NW, NFIX, TRAIN, PAD>), dim3(h->blocks), dim3(h->threads), h->lds, s, P);
+  hipLaunchKernelGGL((rvo3d::env_kernel<MODE, NW, NFIX, TRAIN, PAD>), dim3(h->geo.blocks), dim3(h->geo.threads), h->geo.lds, s, P);
 }
 template <int MODE, int NW, int NFIX, bool PAD>
 void launch_train(rvo3d_env* h, const Params& P, hipStream_t s) {
@@ -364,6 +334,18 @@ int policy_mlp_sample(const void* blob, int32_t obs_width, const float* obs, int
     default: return launch_policy_mlp<X3, 8>(A, grid, s);
   }
 }
+
+// The scalar per-drone fields of rvo3d_get_state / rvo3d_set_state in the order both copy them:
+// the caller's array (null: skipped), the arena's, bytes.
+struct ScalarField { const void* caller; void* arena; size_t bytes; };
+std::array<ScalarField, 8> scalar_fields(const Params& P, const double* yaw, const double* pitch, const double* real_len,
+                                         const double* max_dev, const double* extra_len, const int32_t* wp_idx,
+                                         const uint8_t* arrive, const uint8_t* dest) {
+  const size_t EN = (size_t)(P.E * P.N);
+  return {{{yaw, P.yaw(), EN * 8}, {pitch, P.pitch(), EN * 8}, {real_len, P.real_len(), EN * 8},
+           {max_dev, P.max_dev(), EN * 8}, {extra_len, P.extra_len(), EN * 8}, {wp_idx, P.wp_idx(), EN * 4},
+           {arrive, P.arrive(), EN}, {dest, P.dest(), EN}}};
+}
 }  // namespace
 
 extern "C" {
@@ -398,126 +380,17 @@ int rvo3d_create(const rvo3d_config* cfg, rvo3d_env** out) {
   } owner{h};
   h->cfg = *cfg;
   Params& P = h->P;
-  rvo3d::Cold& C = h->cold;
-  std::memset(&P, 0, sizeof P);
-  std::memset(&C, 0, sizeof C);
-  P.E = cfg->num_envs; P.N = cfg->num_drones; P.P = cfg->max_points;
-  C.nb = cfg->num_buildings; P.nm = cfg->neighbors_num; P.env_train = cfg->env_train ? 1 : 0;
-  P.W = 12 + 9 * P.nm;
+  int lds_pad = 0;
+#ifdef RVO3D_DIAG
+  if (const char* pad = std::getenv("RVO3D_LDS_PAD")) lds_pad = std::atoi(pad);  // diagnostics build only: cap occupancy
+#endif
+  std::string err;
+  if (int rc = rvo3d::plan_env(cfg, lds_pad, P, h->cold, h->geo, err)) return fail(rc, err);
 #ifdef RVO3D_DIAG
   if (const char* ab = std::getenv("RVO3D_ABLATE")) P.ablate = std::atoi(ab);  // diagnostics build only
 #endif
-  C.act_scale = cfg->action_decimals >= 0 ? std::pow(10.0, cfg->action_decimals) : 0.0;
-  for (int k = 0; k < 3; ++k) C.map[k] = cfg->map_size[k];
-  P.T10 = sq_threshold(10.0);  // rvo_inter.py:96
-  C.T5 = sq_threshold(5.0);    // rvo_inter.py:104
-  C.bgx = C.bgy = 0; C.bg_inv = 0.0;
-  if (cfg->num_buildings > 0 && cfg->map_size[0] > 0 && cfg->map_size[1] > 0 &&
-      std::isfinite(cfg->map_size[0]) && std::isfinite(cfg->map_size[1])) {
-    // xy grid for the building gate: ~8 m cells, at most 64 x 64
-    const double cs = std::fmax(8.0, std::fmax(cfg->map_size[0], cfg->map_size[1]) / 64.0);
-    C.bgx = (int)std::ceil(cfg->map_size[0] / cs); C.bgy = (int)std::ceil(cfg->map_size[1] / cs);
-    if (C.bgx < 1) C.bgx = 1;
-    if (C.bgy < 1) C.bgy = 1;
-    C.bg_inv = 1.0 / cs;
-  }
-  C.T04 = sq_threshold(0.4);   // drone.py:15 goal_threshold
-  {
-    // fp32 candidate filter (stage G).  Coordinates are centred on the map and
-    // assumed within cmax of it (envs with a drone further out bypass the filter).
-    // u = 2^-24.  A centred coordinate carries <= u*cmax of rounding, a difference
-    // of two <= eD = u*(2*cmax + 2*10.5); a squared distance at |d| <= 10.5 is off by
-    // <= 2*sqrt(3)*10.5*eD + 3*eD^2 + 8u*10.5^2; v.rel by <= |v|_1*(eD + 4u*10.5).
-    // Every band below is twice its bound.
-    double mx = std::fmax(C.map[0], std::fmax(C.map[1], C.map[2]));
-    if (!(mx > 0)) mx = 1.0;
-    for (int k = 0; k < 3; ++k) C.cen[k] = 0.5 * C.map[k];
-    const double cmax = 0.75 * mx + 16.0;
-    const double u = std::ldexp(1.0, -24);
-    const double eD = u * (2.0 * cmax + 21.0);
-    const double band = 2.0 * (2.0 * 1.7320508 * 10.5 * eD + 3.0 * eD * eD + 8.0 * u * 110.25);
-    C.cmax = (float)cmax;
-    P.band = std::nextafter((float)band, INFINITY);
-    // stage G tests the sign of dx^2 + dy^2 + dz^2 - t' (one fma chain): the chain's own rounding
-    // (<= 3 ulp of ~110) is inside the band, which is twice the bound as it is
-    const float t10f = std::nextafter((float)(P.T10 + band), INFINITY);
-    P.t10n = -std::nextafter(t10f, INFINITY);
-    P.bandn = P.band + P.t10n;
-    C.kdot = std::nextafter((float)(2.0 * (eD + 4.0 * u * 10.5) * 1.001), INFINITY);
-    // stage X1 (wave mode).  With gap = d^2 - R^2 >= x1_gap = 512*band the relative
-    // error of gap is <= 1/1024 and |rel| >= sqrt(gap); a direction cosine then
-    // carries <= cs = 4*(sqrt(3)*eD/sqrt(gap) + 8u) of error.  K^2 is compared with
-    // slack 1 - (4e-3 + 4*cs): 2e-3 for gap's error, the rest for dp, w2 and K.
-    const double gap = 512.0 * band;
-    const double cs = 4.0 * (1.7320508 * eD / std::sqrt(gap) + 8.0 * u);
-    P.x1_gap = (float)gap;
-    P.x1_k2 = (float)(1.0 - (4e-3 + 4.0 * cs));
-    const double cs_out = cs > 1e-3 ? cs : 1e-3;
-    P.x1_cs2 = (float)(cs_out * cs_out);
-  }
-
-  // Launch geometry: whole envs per workgroup.  N <= 64: a workgroup is ONE wave holding
-  // floor(64 / N) envs (its barriers are free, every wave is scheduled independently);
-  // larger envs get one workgroup of ceil(N / 64) waves each.
-  const int N = P.N;
-  int nw = (N + 63) / 64;
-  P.nw = nw <= 4 ? nw : 8;  // 1..4 waves: the compile-time kernels for 64 / 128 / 192 / 256 drones; beyond: generic
-  int epb = P.nw == 1 ? 64 / N : 1;
-  if (epb > P.E) epb = P.E;
-  // nw = 2 / 3 / 4: the compile-time kernels for 128 / 192 / 256 drones, any N up to that (ghost lanes)
-  const int ring = (P.nw >= 2 && P.nw <= 4) ? 64 * P.nw : N;
-  const int threads = P.nw == 1 ? 64 : (int)align_up((size_t)ring, 64);
-  size_t lds = rvo3d::lds_bytes(threads, P.nm, epb, ring, P.nw);
-#ifdef RVO3D_DIAG
-  if (const char* pad = std::getenv("RVO3D_LDS_PAD")) lds += (size_t)std::atoi(pad);  // diagnostics build only: cap occupancy
-#endif
-  if (lds > 160 * 1024) {
-    return fail(RVO3D_ERR_INVALID, "neighbors_num * num_drones needs more than 160 KiB of LDS");
-  }
-  P.epb = epb;
-  // zero-fill geometry: units per row of the VO region (float2 if rows are 8-B aligned)
-  C.zf_div = (uint32_t)((P.W & 1) == 0 ? (P.W - 12) / 2 : (P.W - 12));
-  C.zf_magic = 0;
-  if (C.zf_div > 0) {
-    const uint32_t m = (uint32_t)(((1ull << 32) + C.zf_div - 1) / C.zf_div);
-    bool ok = true;
-    const uint64_t qmax = (uint64_t)threads * C.zf_div;
-    for (uint64_t q = 0; q < qmax && ok; ++q) ok = ((q * m) >> 32) == q / C.zf_div;
-    if (!ok) {
-      return fail(RVO3D_ERR_INVALID, "neighbors_num too large for the zero-fill index trick");
-    }
-    C.zf_magic = m;
-  }
-  C.zf_q = (P.W & 1) == 0 ? (uint32_t)(P.W / 2) : 0u;  // row bytes / 8: the 16-B row writer applies
-  // early_zero_blocks: which of its trips a thread quad stores in depends on W and the quad only
-  C.zf_iters = 0;
-  static_assert(rvo3d::kMaxThreads / 4 <= sizeof(C.zmask) / sizeof(C.zmask[0]),
-                "Cold::zmask has one word per thread quad of the largest workgroup");
-  std::memset(C.zmask, 0, sizeof C.zmask);
-  {
-    const uint32_t rb = 4u * (uint32_t)P.W;
-    const uint32_t rows_full = (uint32_t)epb * (uint32_t)N, nwv = (uint32_t)threads / 64u;
-    const uint32_t nblk = rows_full * rb >> 6;
-    const uint32_t iters = (nblk + 16u * nwv - 1u) / (16u * nwv);
-    if (C.zf_q != 0 && P.W >= 48 && (rows_full & 7u) == 0 && iters <= 32u) {
-      for (uint32_t tq = 0; tq < (uint32_t)threads / 4u; ++tq) {
-        uint32_t m = 0;
-        for (uint32_t i = 0; i < iters; ++i) {
-          const uint32_t blk = tq + 16u * nwv * i;  // tq = wave * 16 + (lane / 4)
-          if (blk >= nblk) break;
-          const uint32_t o = (blk * 64u) % rb;
-          if (o >= 48u && o + 64u <= rb) m |= 1u << i;
-        }
-        C.zmask[tq] = m;
-      }
-      C.zf_iters = (int)iters;
-    }
-  }
-  h->threads = threads;
-  h->blocks = (P.E + epb - 1) / epb;
-  h->lds = (int)lds;
-  if (lds > 64 * 1024) {
-    const bool ok = P.nw == 1 ? allow_lds_all<1>((int)lds) : (P.nw == 8 && allow_lds_all<8>((int)lds));
+  if (h->geo.lds > 64 * 1024) {
+    const bool ok = P.nw == 1 ? allow_lds_all<1>(h->geo.lds) : (P.nw == 8 && allow_lds_all<8>(h->geo.lds));
     if (!ok) {
       return fail(RVO3D_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
     }
@@ -555,82 +428,22 @@ int rvo3d_load_world(rvo3d_env* h, const double* waypoints, const int32_t* n_poi
   if (C.nb > 0 && !buildings) return fail(RVO3D_ERR_INVALID, "buildings required when num_buildings > 0");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t EN = (size_t)P.E * P.N;
-  std::vector<double> wp((size_t)P.P * 3 * EN), rl(EN), rad(EN), pri(EN), p95(P.P);
-  for (size_t g = 0; g < EN; ++g) {
-    const int np = n_points[g];
-    if (np < 2 || np > P.P) return fail(RVO3D_ERR_INVALID, "n_points entries must be in [2, max_points]");
-    const double* src = waypoints + g * P.P * 3;
-    double total = 0.0;  // drone.calculate_total_length (drone.py:409-429)
-    for (int k = 0; k < P.P; ++k) {
-      const int kk = k < np ? k : np - 1;  // pad with the destination
-      for (int c = 0; c < 3; ++c) wp[((size_t)k * 3 + c) * EN + g] = src[kk * 3 + c];
-      if (k + 1 < np) {
-        const double dx = src[(k + 1) * 3] - src[k * 3], dy = src[(k + 1) * 3 + 1] - src[k * 3 + 1],
-                     dz = src[(k + 1) * 3 + 2] - src[k * 3 + 2];
-        total += std::sqrt(py_sq(dx) + py_sq(dy) + py_sq(dz));
-      }
-    }
-    rl[g] = total;
-    rad[g] = radius ? radius[g] : 0.2;
-    pri[g] = priority ? priority[g] : 5.0;
-  }
-  {
-    // one radius and one priority for every drone (bit-identical doubles): the step takes them from
-    // its argument block instead of reading 16 B per drone-step
-    bool uni = true;
-    for (size_t g = 1; g < EN && uni; ++g)
-      uni = std::memcmp(&rad[g], &rad[0], 8) == 0 && std::memcmp(&pri[g], &pri[0], 8) == 0;
-    h->P.uniform_rp = uni ? 1 : 0;
-    h->P.r0 = rad[0];
-    h->P.prio0 = pri[0];
-  }
-  for (int k = 0; k < P.P; ++k) p95[k] = std::pow(0.95, (double)k);  // ir_gym.py:283
+  rvo3d::StagedWorld w;
+  std::string err;
+  if (int rc2 = rvo3d::stage_world(h->P, waypoints, n_points, radius, priority, w, err)) return fail(rc2, err);
   // [P][3] rows of EN doubles into arrays of stride S
-  HIP_TRY(hipMemcpy2DAsync((void*)P.wp(0, 0), (size_t)P.S * 8, wp.data(), EN * 8, EN * 8,
+  HIP_TRY(hipMemcpy2DAsync((void*)P.wp(0, 0), (size_t)P.S * 8, w.wp.data(), EN * 8, EN * 8,
                            (size_t)P.P * 3, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync((void*)P.n_points(), n_points, EN * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync((void*)P.route_len(), rl.data(), EN * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync((void*)P.radius(), rad.data(), EN * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync((void*)P.prio(), pri.data(), EN * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync((void*)C.pow95, p95.data(), (size_t)P.P * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync((void*)P.route_len(), w.rl.data(), EN * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync((void*)P.radius(), w.rad.data(), EN * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync((void*)P.prio(), w.pri.data(), EN * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync((void*)C.pow95, w.p95.data(), (size_t)P.P * 8, hipMemcpyHostToDevice, s));
   std::vector<uint16_t> grid;
   if (C.nb > 0) {
     HIP_TRY(hipMemcpyAsync((void*)C.bld, buildings, (size_t)C.nb * 32, hipMemcpyHostToDevice, s));
     if (C.bgx > 0) {
-      // cell (ix, iy) = [ix*cs, (ix+1)*cs] x [iy*cs, (iy+1)*cs], widened by 1e-3 m (the device
-      // finds the cell with floor(x / cs) in floating point) and unbounded at the map's edge
-      // (clamped lookups); a building is listed where a drone inside the cell could hit it:
-      // within the 5 m gate AND within (largest drone radius + building radius) of its axis
-      // (rvo_inter.py:104, :207) - with 0.2 m drones that is 2 cells per building instead of 5
-      const int K = rvo3d::kBgridK;
-      const double cs = 1.0 / C.bg_inv;
-      double rmax = 0.0;
-      for (size_t g = 0; g < EN; ++g) {
-        if (rad[g] != rad[g]) rmax = INFINITY;  // a NaN radius: no pruning beyond the gate
-        else if (rad[g] > rmax) rmax = rad[g];
-      }
-      grid.assign((size_t)C.bgx * C.bgy * (K + 1), 0);
-      for (int ix = 0; ix < C.bgx; ++ix)
-        for (int iy = 0; iy < C.bgy; ++iy) {
-          uint16_t* cell = &grid[((size_t)ix * C.bgy + iy) * (K + 1)];
-          const double x0 = ix == 0 ? -INFINITY : ix * cs, x1 = ix == C.bgx - 1 ? INFINITY : (ix + 1) * cs;
-          const double y0 = iy == 0 ? -INFINITY : iy * cs, y1 = iy == C.bgy - 1 ? INFINITY : (iy + 1) * cs;
-          int n = 0;
-          bool overflow = false;
-          for (int b = 0; b < C.nb && !overflow; ++b) {
-            const double bx = buildings[4 * b], by = buildings[4 * b + 1];
-            double reach = rmax + buildings[4 * b + 3];
-            if (!(reach < 5.0)) reach = 5.0;  // the gate (also a NaN radius)
-            reach += 1e-3;
-            const double dx = bx < x0 ? x0 - bx : (bx > x1 ? bx - x1 : 0.0);
-            const double dy = by < y0 ? y0 - by : (by > y1 ? by - y1 : 0.0);
-            if (!(dx * dx + dy * dy > reach * reach)) {  // also keeps NaN centres
-              if (n == K || b > 0xfffe) overflow = true;
-              else cell[1 + n++] = (uint16_t)b;
-            }
-          }
-          cell[0] = overflow ? 0xffff : (uint16_t)n;
-        }
+      grid = rvo3d::build_building_grid(C, buildings, w.rad);
       HIP_TRY(hipMemcpyAsync((void*)C.bgrid, grid.data(), grid.size() * 2, hipMemcpyHostToDevice, s));
     }
   }
@@ -693,54 +506,43 @@ int rvo3d_observe(rvo3d_env* h, float* obs, int32_t* vo_count, void* stream) {
   RVO3D_API_END
 }
 
-static int step_common(rvo3d_env* h, const void* actions, int32_t action_dtype, float* obs,
-                       int32_t* vo_count, float* reward, uint8_t* done, uint8_t* info,
-                       uint8_t* finish, uint8_t* reset_mask, bool autoreset, void* stream,
-                       const int32_t* prev_cnt = nullptr) {
-  RVO3D_API_BEGIN
+// The one implementation behind the four step entry points (called between their RVO3D_API_BEGIN / END).  Policy
+// mode lives in the per-call Params copy alone: of h it writes nothing but the two cache flags.
+static int step_impl(rvo3d_env* h, const rvo3d_step_args& a, void* stream) {
   DeviceGuard dg;
   int rc = check(h, true, dg);
   if (rc) return rc;
-  if (!actions || !obs || !vo_count || !reward || !done || !info || !finish)
+  if (!a.actions || !a.obs || !a.vo_count || !a.reward || !a.done || !a.info || !a.finish)
     return fail(RVO3D_ERR_INVALID, "null I/O pointer");
+  const int32_t action_dtype = a.policy ? RVO3D_F32 : a.action_dtype;
   if (action_dtype != RVO3D_F32 && action_dtype != RVO3D_F64)
     return fail(RVO3D_ERR_INVALID, "action_dtype must be RVO3D_F32 or RVO3D_F64");
   Params P = h->P;
-  P.actions = actions; P.action_f64 = action_dtype == RVO3D_F64;
-  P.obs = obs; P.vo_count = vo_count; P.reward = reward;
-  P.zf16 = (h->cold.zf_q != 0 && (reinterpret_cast<uintptr_t>(obs) & 15) == 0 && P.nm > 0) ? 1 : 0;
-  P.done = done; P.info = info; P.finish = finish; P.reset_mask = reset_mask;
-  P.prev_cnt = prev_cnt;  // (h->P's is always null: nothing of it outlives the call)
+  P.action_mode = a.policy ? 1 : 0;
+  P.acceler = a.acceler;
+  P.actions = a.actions; P.action_f64 = action_dtype == RVO3D_F64;
+  P.obs = a.obs; P.vo_count = a.vo_count; P.reward = a.reward;
+  P.zf16 = (h->cold.zf_q != 0 && (reinterpret_cast<uintptr_t>(a.obs) & 15) == 0 && P.nm > 0) ? 1 : 0;
+  P.done = a.done; P.info = a.info; P.finish = a.finish;
+  // the absolute step hands out a reset mask only with auto-reset; the policy step takes it as given
+  P.reset_mask = (a.policy || a.autoreset) ? a.reset_mask : nullptr;
+  P.prev_cnt = a.prev_vo_count;  // (h->P's is always null: nothing of it outlives the call)
   P.dv_cached = h->dv_valid ? 1 : 0;
   P.g_cached = h->g_valid ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  rc = autoreset ? launch<rvo3d::kStepAutoReset>(h, P, s) : launch<rvo3d::kStep>(h, P, s);
+  rc = a.autoreset ? launch<rvo3d::kStepAutoReset>(h, P, s) : launch<rvo3d::kStep>(h, P, s);
   if (rc == RVO3D_OK) h->dv_valid = h->g_valid = true;  // every step files both for the state it ends in
   return rc;
-  RVO3D_API_END
 }
 
 int rvo3d_step(rvo3d_env* h, const void* actions, int32_t action_dtype, float* obs,
                int32_t* vo_count, float* reward, uint8_t* done, uint8_t* info, uint8_t* finish,
                void* stream) {
   RVO3D_API_BEGIN
-  return step_common(h, actions, action_dtype, obs, vo_count, reward, done, info, finish, nullptr,
-                     false, stream);
-  RVO3D_API_END
-}
-
-static int step_policy_common(rvo3d_env* h, const float* a_inc, float acceler, float* obs,
-                              int32_t* vo_count, float* reward, uint8_t* done, uint8_t* info,
-                              uint8_t* finish, uint8_t* reset_mask, bool autoreset, void* stream,
-                              const int32_t* prev_cnt = nullptr) {
-  RVO3D_API_BEGIN
-  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
-  h->P.action_mode = 1;
-  h->P.acceler = acceler;
-  const int rc = step_common(h, a_inc, RVO3D_F32, obs, vo_count, reward, done, info, finish,
-                             reset_mask, autoreset, stream, prev_cnt);
-  h->P.action_mode = 0;
-  return rc;
+  rvo3d_step_args a{};
+  a.actions = actions; a.action_dtype = action_dtype;
+  a.obs = obs; a.vo_count = vo_count; a.reward = reward; a.done = done; a.info = info; a.finish = finish;
+  return step_impl(h, a, stream);
   RVO3D_API_END
 }
 
@@ -748,8 +550,11 @@ int rvo3d_step_policy(rvo3d_env* h, const float* a_inc, float acceler, float* ob
                       int32_t* vo_count, float* reward, uint8_t* done, uint8_t* info,
                       uint8_t* finish, uint8_t* reset_mask, int32_t autoreset, void* stream) {
   RVO3D_API_BEGIN
-  return step_policy_common(h, a_inc, acceler, obs, vo_count, reward, done, info, finish,
-                            reset_mask, autoreset != 0, stream);
+  rvo3d_step_args a{};
+  a.actions = a_inc; a.policy = 1; a.acceler = acceler; a.autoreset = autoreset;
+  a.obs = obs; a.vo_count = vo_count; a.reward = reward; a.done = done; a.info = info; a.finish = finish;
+  a.reset_mask = reset_mask;
+  return step_impl(h, a, stream);
   RVO3D_API_END
 }
 
@@ -757,20 +562,18 @@ int rvo3d_step_autoreset(rvo3d_env* h, const void* actions, int32_t action_dtype
                          int32_t* vo_count, float* reward, uint8_t* done, uint8_t* info,
                          uint8_t* finish, uint8_t* reset_mask, void* stream) {
   RVO3D_API_BEGIN
-  return step_common(h, actions, action_dtype, obs, vo_count, reward, done, info, finish,
-                     reset_mask, true, stream);
+  rvo3d_step_args a{};
+  a.actions = actions; a.action_dtype = action_dtype; a.autoreset = 1;
+  a.obs = obs; a.vo_count = vo_count; a.reward = reward; a.done = done; a.info = info; a.finish = finish;
+  a.reset_mask = reset_mask;
+  return step_impl(h, a, stream);
   RVO3D_API_END
 }
 
 int rvo3d_step_ex(rvo3d_env* h, const rvo3d_step_args* a, void* stream) {
   RVO3D_API_BEGIN
   if (!a) return fail(RVO3D_ERR_INVALID, "null argument");
-  if (a->policy)
-    return step_policy_common(h, static_cast<const float*>(a->actions), a->acceler, a->obs, a->vo_count, a->reward,
-                              a->done, a->info, a->finish, a->reset_mask, a->autoreset != 0, stream,
-                              a->prev_vo_count);
-  return step_common(h, a->actions, a->action_dtype, a->obs, a->vo_count, a->reward, a->done, a->info, a->finish,
-                     a->autoreset ? a->reset_mask : nullptr, a->autoreset != 0, stream, a->prev_vo_count);
+  return step_impl(h, *a, stream);
   RVO3D_API_END
 }
 
@@ -1118,14 +921,8 @@ int rvo3d_get_state(rvo3d_env* h, double* pos, double* vel, double* yaw, double*
   if (vel) hipLaunchKernelGGL(rvo3d::soa_to_aos3, grid, blk, 0, s, P.vx(), P.vy(), P.vz(), vel, EN);
   HIP_TRY(hipGetLastError());
   const hipMemcpyKind k = hipMemcpyDeviceToDevice;
-  if (yaw) HIP_TRY(hipMemcpyAsync(yaw, P.yaw(), (size_t)EN * 8, k, s));
-  if (pitch) HIP_TRY(hipMemcpyAsync(pitch, P.pitch(), (size_t)EN * 8, k, s));
-  if (real_len) HIP_TRY(hipMemcpyAsync(real_len, P.real_len(), (size_t)EN * 8, k, s));
-  if (max_dev) HIP_TRY(hipMemcpyAsync(max_dev, P.max_dev(), (size_t)EN * 8, k, s));
-  if (extra_len) HIP_TRY(hipMemcpyAsync(extra_len, P.extra_len(), (size_t)EN * 8, k, s));
-  if (wp_idx) HIP_TRY(hipMemcpyAsync(wp_idx, P.wp_idx(), (size_t)EN * 4, k, s));
-  if (arrive) HIP_TRY(hipMemcpyAsync(arrive, P.arrive(), (size_t)EN, k, s));
-  if (dest) HIP_TRY(hipMemcpyAsync(dest, P.dest(), (size_t)EN, k, s));
+  for (const ScalarField& f : scalar_fields(P, yaw, pitch, real_len, max_dev, extra_len, wp_idx, arrive, dest))
+    if (f.caller) HIP_TRY(hipMemcpyAsync(const_cast<void*>(f.caller), f.arena, f.bytes, k, s));
   return RVO3D_OK;
   RVO3D_API_END
 }
@@ -1147,17 +944,12 @@ int rvo3d_set_state(rvo3d_env* h, const double* pos, const double* vel, const do
   if (vel) hipLaunchKernelGGL(rvo3d::aos3_to_soa, grid, blk, 0, s, vel, P.vx(), P.vy(), P.vz(), EN);
   HIP_TRY(hipGetLastError());
   const hipMemcpyKind k = hipMemcpyDeviceToDevice;
-  if (yaw) HIP_TRY(hipMemcpyAsync(P.yaw(), yaw, (size_t)EN * 8, k, s));
-  if (pitch) HIP_TRY(hipMemcpyAsync(P.pitch(), pitch, (size_t)EN * 8, k, s));
-  if (real_len) HIP_TRY(hipMemcpyAsync(P.real_len(), real_len, (size_t)EN * 8, k, s));
-  if (max_dev) HIP_TRY(hipMemcpyAsync(P.max_dev(), max_dev, (size_t)EN * 8, k, s));
-  if (extra_len) HIP_TRY(hipMemcpyAsync(P.extra_len(), extra_len, (size_t)EN * 8, k, s));
-  if (wp_idx) {  // current / previous waypoint follow the index
-    HIP_TRY(hipMemcpyAsync(P.wp_idx(), wp_idx, (size_t)EN * 4, k, s));
-    hipLaunchKernelGGL(rvo3d::wpcache_kernel, grid, blk, 0, s, P);
+  for (const ScalarField& f : scalar_fields(P, yaw, pitch, real_len, max_dev, extra_len, wp_idx, arrive, dest)) {
+    if (!f.caller) continue;
+    HIP_TRY(hipMemcpyAsync(f.arena, f.caller, f.bytes, k, s));
+    // current / previous waypoint follow the index
+    if (f.arena == P.wp_idx()) hipLaunchKernelGGL(rvo3d::wpcache_kernel, grid, blk, 0, s, P);
   }
-  if (arrive) HIP_TRY(hipMemcpyAsync(P.arrive(), arrive, (size_t)EN, k, s));
-  if (dest) HIP_TRY(hipMemcpyAsync(P.dest(), dest, (size_t)EN, k, s));
   return RVO3D_OK;
   RVO3D_API_END
 }
@@ -1203,10 +995,10 @@ int rvo3d_launch_info(rvo3d_env* h, int32_t* threads, int32_t* envs_per_block, i
                       int32_t* lds_bytes) {
   RVO3D_API_BEGIN
   if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
-  if (threads) *threads = h->threads;
+  if (threads) *threads = h->geo.threads;
   if (envs_per_block) *envs_per_block = h->P.epb;
-  if (blocks) *blocks = h->blocks;
-  if (lds_bytes) *lds_bytes = h->lds;
+  if (blocks) *blocks = h->geo.blocks;
+  if (lds_bytes) *lds_bytes = h->geo.lds;
   return RVO3D_OK;
   RVO3D_API_END
 }

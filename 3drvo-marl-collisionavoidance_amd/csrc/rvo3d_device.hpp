@@ -24,9 +24,9 @@
 // (compile with -ffp-contract=off; the explicit __builtin_fma calls model the
 // OpenBLAS ddot the reference goes through, see DESIGN.md "arithmetic model").
 // Reference citations are relative to the reference root.
-#pragma once
 //
-// Files: rvo3d_params.hpp (parameter blocks), rvo3d_math.hpp (arithmetic model, per-drone
+// Files: rvo3d_params.hpp (parameter blocks), rvo3d_host_setup.hpp (what the host derives for a handle: bands,
+// launch geometry, tables, the staged world; host only), rvo3d_math.hpp (arithmetic model, per-drone
 // pieces), rvo3d_lds.hpp (LDS views), rvo3d_pairs.hpp (pair pipeline), rvo3d_step.hpp (the step
 // kernel), rvo3d_aux_kernels.hpp (resets, tables, classical RVO selection), rvo3d_rollout_kernels.hpp (the
 // trainer's per-step glue: policy heads + sampling, episode bookkeeping), rvo3d_mfma_tiles.hpp (what the three

@@ -1,0 +1,276 @@
+// rvo3d_host_setup.hpp -- what the host computes for an env handle before anything is allocated: thresholds,
+// the float32 error bands, launch geometry, the zero-fill tables, the building grid, the staged world.
+// Host only: no function here calls HIP or reads the environment, so tests/host/host_setup_check.hip runs
+// all of it on a machine without a GPU.  Failures come back as a status of include/rvo3d.h plus a message.
+#pragma once
+
+#include "../../include/rvo3d.h"
+#include "rvo3d_params.hpp"
+#include "rvo3d_lds.hpp"
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace rvo3d {
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// x ** 2 as the reference computes it: glibc pow (the volatile exponent keeps
+// the compiler from folding the call into x * x).
+inline volatile double kTwo = 2.0;
+inline double py_sq(double x) { return std::pow(x, kTwo); }
+
+// max{x : sqrt(x) <= tau} for the host's correctly rounded sqrt: `norm <= tau`
+// in the reference is exactly `norm^2 <= sq_threshold(tau)` on the device.
+inline double sq_threshold(double tau) {
+  volatile double x = tau * tau;
+  while (std::sqrt(std::nextafter((double)x, INFINITY)) <= tau) x = std::nextafter((double)x, INFINITY);
+  while (std::sqrt((double)x) > tau) x = std::nextafter((double)x, -INFINITY);
+  return x;
+}
+
+// Which instantiation a handle's shape runs on: the compile-time ring size NFIX (0 = the generic kernel of
+// its NW) and whether N is smaller than it (padded: ghost lanes).  One place decides; launch_nw() launches
+// it and rvo3d_kernel_name() reports it.
+struct Pick { int nfix; bool pad; };
+inline Pick pick_kernel(const Params& P) {
+  if (P.nw == 1) {
+    // a one-wave workgroup of epb envs: segments of 64 / epb lanes
+    const int seg = (P.epb == 1 || P.epb == 2 || P.epb == 4) ? 64 / P.epb : 0;
+    if (seg && P.N == seg) return {seg, false};
+    if (seg >= 32 && P.N < seg) return {seg, true};  // 33..63 drones on the 64 kernel, 22..31 on the 32 one
+    return {0, false};
+  }
+  // multi-wave workgroups: the compile-time kernels take any N up to their size
+  if (P.nw == 2) return {128, true};
+  if (P.nw == 3) return {192, true};
+  if (P.nw == 4) return {256, true};
+  return {0, false};
+}
+
+// xy grid for the building gate: ~8 m cells, at most 64 x 64 (bgx == 0: no grid)
+inline void building_grid_dims(const rvo3d_config* cfg, Cold& C) {
+  C.bgx = C.bgy = 0; C.bg_inv = 0.0;
+  if (cfg->num_buildings > 0 && cfg->map_size[0] > 0 && cfg->map_size[1] > 0 &&
+      std::isfinite(cfg->map_size[0]) && std::isfinite(cfg->map_size[1])) {
+    const double cs = std::fmax(8.0, std::fmax(cfg->map_size[0], cfg->map_size[1]) / 64.0);
+    C.bgx = (int)std::ceil(cfg->map_size[0] / cs); C.bgy = (int)std::ceil(cfg->map_size[1] / cs);
+    if (C.bgx < 1) C.bgx = 1;
+    if (C.bgy < 1) C.bgy = 1;
+    C.bg_inv = 1.0 / cs;
+  }
+}
+
+// The float32 error bands of stage G and stage X1, from C.map and P.T10.
+inline void filter_bands(Params& P, Cold& C) {
+  // fp32 candidate filter (stage G).  Coordinates are centred on the map and
+  // assumed within cmax of it (envs with a drone further out bypass the filter).
+  // u = 2^-24.  A centred coordinate carries <= u*cmax of rounding, a difference
+  // of two <= eD = u*(2*cmax + 2*10.5); a squared distance at |d| <= 10.5 is off by
+  // <= 2*sqrt(3)*10.5*eD + 3*eD^2 + 8u*10.5^2; v.rel by <= |v|_1*(eD + 4u*10.5).
+  // Every band below is twice its bound.
+  double mx = std::fmax(C.map[0], std::fmax(C.map[1], C.map[2]));
+  if (!(mx > 0)) mx = 1.0;
+  for (int k = 0; k < 3; ++k) C.cen[k] = 0.5 * C.map[k];
+  const double cmax = 0.75 * mx + 16.0;
+  const double u = std::ldexp(1.0, -24);
+  const double eD = u * (2.0 * cmax + 21.0);
+  const double band = 2.0 * (2.0 * 1.7320508 * 10.5 * eD + 3.0 * eD * eD + 8.0 * u * 110.25);
+  C.cmax = (float)cmax;
+  P.band = std::nextafter((float)band, INFINITY);
+  // stage G tests the sign of dx^2 + dy^2 + dz^2 - t' (one fma chain): the chain's own rounding
+  // (<= 3 ulp of ~110) is inside the band, which is twice the bound as it is
+  const float t10f = std::nextafter((float)(P.T10 + band), INFINITY);
+  P.t10n = -std::nextafter(t10f, INFINITY);
+  P.bandn = P.band + P.t10n;
+  C.kdot = std::nextafter((float)(2.0 * (eD + 4.0 * u * 10.5) * 1.001), INFINITY);
+  // stage X1 (wave mode).  With gap = d^2 - R^2 >= x1_gap = 512*band the relative
+  // error of gap is <= 1/1024 and |rel| >= sqrt(gap); a direction cosine then
+  // carries <= cs = 4*(sqrt(3)*eD/sqrt(gap) + 8u) of error.  K^2 is compared with
+  // slack 1 - (4e-3 + 4*cs): 2e-3 for gap's error, the rest for dp, w2 and K.
+  const double gap = 512.0 * band;
+  const double cs = 4.0 * (1.7320508 * eD / std::sqrt(gap) + 8.0 * u);
+  P.x1_gap = (float)gap;
+  P.x1_k2 = (float)(1.0 - (4e-3 + 4.0 * cs));
+  const double cs_out = cs > 1e-3 ? cs : 1e-3;
+  P.x1_cs2 = (float)(cs_out * cs_out);
+}
+
+struct Geometry { int threads, blocks, lds; };
+
+// Launch geometry: whole envs per workgroup.  N <= 64: a workgroup is ONE wave holding
+// floor(64 / N) envs (its barriers are free, every wave is scheduled independently);
+// larger envs get one workgroup of ceil(N / 64) waves each.
+// (lds_pad: the diagnostics build's extra LDS bytes, which cap occupancy; 0 in the product)
+inline int launch_geometry(int lds_pad, Params& P, Geometry& G, std::string& err) {
+  const int N = P.N;
+  int nw = (N + 63) / 64;
+  P.nw = nw <= 4 ? nw : 8;  // 1..4 waves: the compile-time kernels for 64 / 128 / 192 / 256 drones; beyond: generic
+  int epb = P.nw == 1 ? 64 / N : 1;
+  if (epb > P.E) epb = P.E;
+  // nw = 2 / 3 / 4: the compile-time kernels for 128 / 192 / 256 drones, any N up to that (ghost lanes)
+  const int ring = (P.nw >= 2 && P.nw <= 4) ? 64 * P.nw : N;
+  const int threads = P.nw == 1 ? 64 : (int)align_up((size_t)ring, 64);
+  size_t lds = lds_bytes(threads, P.nm, epb, ring, P.nw);
+  lds += (size_t)lds_pad;
+  if (lds > 160 * 1024) {
+    err = "neighbors_num * num_drones needs more than 160 KiB of LDS";
+    return RVO3D_ERR_INVALID;
+  }
+  P.epb = epb;
+  G.threads = threads;
+  G.blocks = (P.E + epb - 1) / epb;
+  G.lds = (int)lds;
+  return RVO3D_OK;
+}
+
+// The zero-fill index divisor with its magic multiplier, and the two-phase row writer's table.
+inline int zero_fill_tables(const Params& P, int threads, Cold& C, std::string& err) {
+  const int N = P.N, epb = P.epb;
+  // zero-fill geometry: units per row of the VO region (float2 if rows are 8-B aligned)
+  C.zf_div = (uint32_t)((P.W & 1) == 0 ? (P.W - 12) / 2 : (P.W - 12));
+  C.zf_magic = 0;
+  if (C.zf_div > 0) {
+    const uint32_t m = (uint32_t)(((1ull << 32) + C.zf_div - 1) / C.zf_div);
+    bool ok = true;
+    const uint64_t qmax = (uint64_t)threads * C.zf_div;
+    for (uint64_t q = 0; q < qmax && ok; ++q) ok = ((q * m) >> 32) == q / C.zf_div;
+    if (!ok) {
+      err = "neighbors_num too large for the zero-fill index trick";
+      return RVO3D_ERR_INVALID;
+    }
+    C.zf_magic = m;
+  }
+  C.zf_q = (P.W & 1) == 0 ? (uint32_t)(P.W / 2) : 0u;  // row bytes / 8: the 16-B row writer applies
+  // early_zero_blocks: which of its trips a thread quad stores in depends on W and the quad only
+  C.zf_iters = 0;
+  static_assert(kMaxThreads / 4 <= sizeof(C.zmask) / sizeof(C.zmask[0]),
+                "Cold::zmask has one word per thread quad of the largest workgroup");
+  std::memset(C.zmask, 0, sizeof C.zmask);
+  {
+    const uint32_t rb = 4u * (uint32_t)P.W;
+    const uint32_t rows_full = (uint32_t)epb * (uint32_t)N, nwv = (uint32_t)threads / 64u;
+    const uint32_t nblk = rows_full * rb >> 6;
+    const uint32_t iters = (nblk + 16u * nwv - 1u) / (16u * nwv);
+    if (C.zf_q != 0 && P.W >= 48 && (rows_full & 7u) == 0 && iters <= 32u) {
+      for (uint32_t tq = 0; tq < (uint32_t)threads / 4u; ++tq) {
+        uint32_t m = 0;
+        for (uint32_t i = 0; i < iters; ++i) {
+          const uint32_t blk = tq + 16u * nwv * i;  // tq = wave * 16 + (lane / 4)
+          if (blk >= nblk) break;
+          const uint32_t o = (blk * 64u) % rb;
+          if (o >= 48u && o + 64u <= rb) m |= 1u << i;
+        }
+        C.zmask[tq] = m;
+      }
+      C.zf_iters = (int)iters;
+    }
+  }
+  return RVO3D_OK;
+}
+
+// Everything rvo3d_create derives from a checked config, in one go: Params and Cold without their
+// pointers, and the launch geometry.
+inline int plan_env(const rvo3d_config* cfg, int lds_pad, Params& P, Cold& C, Geometry& G, std::string& err) {
+  std::memset(&P, 0, sizeof P);
+  std::memset(&C, 0, sizeof C);
+  P.E = cfg->num_envs; P.N = cfg->num_drones; P.P = cfg->max_points;
+  C.nb = cfg->num_buildings; P.nm = cfg->neighbors_num; P.env_train = cfg->env_train ? 1 : 0;
+  P.W = 12 + 9 * P.nm;
+  C.act_scale = cfg->action_decimals >= 0 ? std::pow(10.0, cfg->action_decimals) : 0.0;
+  for (int k = 0; k < 3; ++k) C.map[k] = cfg->map_size[k];
+  P.T10 = sq_threshold(10.0);  // rvo_inter.py:96
+  C.T5 = sq_threshold(5.0);    // rvo_inter.py:104
+  building_grid_dims(cfg, C);
+  C.T04 = sq_threshold(0.4);   // drone.py:15 goal_threshold
+  filter_bands(P, C);
+  if (int rc = launch_geometry(lds_pad, P, G, err)) return rc;
+  return zero_fill_tables(P, G.threads, C, err);
+}
+
+// The world as rvo3d_load_world copies it to the device: [P][3] rows of EN waypoint coordinates (padded with
+// the destination), route lengths, radius / priority with the reference's defaults, 0.95 ** k.
+struct StagedWorld { std::vector<double> wp, rl, rad, pri, p95; };
+inline int stage_world(Params& P, const double* waypoints, const int32_t* n_points, const double* radius,
+                       const double* priority, StagedWorld& w, std::string& err) {
+  const size_t EN = (size_t)P.E * P.N;
+  std::vector<double> wp((size_t)P.P * 3 * EN), rl(EN), rad(EN), pri(EN), p95(P.P);
+  for (size_t g = 0; g < EN; ++g) {
+    const int np = n_points[g];
+    if (np < 2 || np > P.P) {
+      err = "n_points entries must be in [2, max_points]";
+      return RVO3D_ERR_INVALID;
+    }
+    const double* src = waypoints + g * P.P * 3;
+    double total = 0.0;  // drone.calculate_total_length (drone.py:409-429)
+    for (int k = 0; k < P.P; ++k) {
+      const int kk = k < np ? k : np - 1;  // pad with the destination
+      for (int c = 0; c < 3; ++c) wp[((size_t)k * 3 + c) * EN + g] = src[kk * 3 + c];
+      if (k + 1 < np) {
+        const double dx = src[(k + 1) * 3] - src[k * 3], dy = src[(k + 1) * 3 + 1] - src[k * 3 + 1],
+                     dz = src[(k + 1) * 3 + 2] - src[k * 3 + 2];
+        total += std::sqrt(py_sq(dx) + py_sq(dy) + py_sq(dz));
+      }
+    }
+    rl[g] = total;
+    rad[g] = radius ? radius[g] : 0.2;
+    pri[g] = priority ? priority[g] : 5.0;
+  }
+  {
+    // one radius and one priority for every drone (bit-identical doubles): the step takes them from
+    // its argument block instead of reading 16 B per drone-step
+    bool uni = true;
+    for (size_t g = 1; g < EN && uni; ++g)
+      uni = std::memcmp(&rad[g], &rad[0], 8) == 0 && std::memcmp(&pri[g], &pri[0], 8) == 0;
+    P.uniform_rp = uni ? 1 : 0;
+    P.r0 = rad[0];
+    P.prio0 = pri[0];
+  }
+  for (int k = 0; k < P.P; ++k) p95[k] = std::pow(0.95, (double)k);  // ir_gym.py:283
+  w.wp.swap(wp); w.rl.swap(rl); w.rad.swap(rad); w.pri.swap(pri); w.p95.swap(p95);
+  return RVO3D_OK;
+}
+
+// The per-cell building lists (C.bgx > 0), kBgridK + 1 u16 per cell.
+inline std::vector<uint16_t> build_building_grid(const Cold& C, const double* buildings, const std::vector<double>& rad) {
+  // cell (ix, iy) = [ix*cs, (ix+1)*cs] x [iy*cs, (iy+1)*cs], widened by 1e-3 m (the device
+  // finds the cell with floor(x / cs) in floating point) and unbounded at the map's edge
+  // (clamped lookups); a building is listed where a drone inside the cell could hit it:
+  // within the 5 m gate AND within (largest drone radius + building radius) of its axis
+  // (rvo_inter.py:104, :207) - with 0.2 m drones that is 2 cells per building instead of 5
+  const size_t EN = rad.size();
+  std::vector<uint16_t> grid;
+  const int K = kBgridK;
+  const double cs = 1.0 / C.bg_inv;
+  double rmax = 0.0;
+  for (size_t g = 0; g < EN; ++g) {
+    if (rad[g] != rad[g]) rmax = INFINITY;  // a NaN radius: no pruning beyond the gate
+    else if (rad[g] > rmax) rmax = rad[g];
+  }
+  grid.assign((size_t)C.bgx * C.bgy * (K + 1), 0);
+  for (int ix = 0; ix < C.bgx; ++ix)
+    for (int iy = 0; iy < C.bgy; ++iy) {
+      uint16_t* cell = &grid[((size_t)ix * C.bgy + iy) * (K + 1)];
+      const double x0 = ix == 0 ? -INFINITY : ix * cs, x1 = ix == C.bgx - 1 ? INFINITY : (ix + 1) * cs;
+      const double y0 = iy == 0 ? -INFINITY : iy * cs, y1 = iy == C.bgy - 1 ? INFINITY : (iy + 1) * cs;
+      int n = 0;
+      bool overflow = false;
+      for (int b = 0; b < C.nb && !overflow; ++b) {
+        const double bx = buildings[4 * b], by = buildings[4 * b + 1];
+        double reach = rmax + buildings[4 * b + 3];
+        if (!(reach < 5.0)) reach = 5.0;  // the gate (also a NaN radius)
+        reach += 1e-3;
+        const double dx = bx < x0 ? x0 - bx : (bx > x1 ? bx - x1 : 0.0);
+        const double dy = by < y0 ? y0 - by : (by > y1 ? by - y1 : 0.0);
+        if (!(dx * dx + dy * dy > reach * reach)) {  // also keeps NaN centres
+          if (n == K || b > 0xfffe) overflow = true;
+          else cell[1 + n++] = (uint16_t)b;
+        }
+      }
+      cell[0] = overflow ? 0xffff : (uint16_t)n;
+    }
+  return grid;
+}
+
+}  // namespace rvo3d

@@ -251,11 +251,7 @@ __device__ __forceinline__ void early_zero_blocks(const Params& P, const Lds& L,
 #pragma unroll
     for (int u = 0; u < 4; ++u)
       if ((m >> u) & 1u) {
-#if RVO3D_ZERO_NT
-        __builtin_nontemporal_store((v4f){0.f, 0.f, 0.f, 0.f}, reinterpret_cast<v4f*>(p + u * step));
-#else
         *reinterpret_cast<v4f*>(p + u * step) = (v4f){0.f, 0.f, 0.f, 0.f};
-#endif
       }
   }
 }
@@ -450,13 +446,6 @@ __device__ __forceinline__ double mov_reward_k(const Params& P, bool collision, 
 
 enum Mode { kObserve = 0, kStep = 1, kStepAutoReset = 2 };
 
-#ifndef RVO3D_ZERO_NT
-#define RVO3D_ZERO_NT 1  // streaming (non-temporal) stores for the early zero blocks
-#endif
-#ifndef RVO3D_DEPHASE
-#define RVO3D_DEPHASE 0
-#endif
-
 // 128 VGPRs = 4 waves per SIMD.  One-wave workgroups (N <= 64): the 4096 waves of 64 x 4096 are
 // all resident at once.  N <= 256 (one env per workgroup of 2 or 4 waves): the fourth wave per
 // SIMD is what lets 4 workgroups of 256 drones (40 KB of LDS each) share a CU, and shortens the
@@ -510,15 +499,6 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   // stored as soon as they are final, so that across the sweeps little more than the
   // drone's own 8-value record and its action stay live (registers = waves per SIMD).
   RVO3D_STAMP(0);
-#if RVO3D_DEPHASE
-  // (experiment, off) waves in odd slots of their SIMD start RVO3D_DEPHASE x ~0.94 us (2048 cycles) late
-  if (NW == 1) {
-    unsigned hw_slot;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_slot));
-    if (hw_slot & 1)
-      for (int i = 0; i < RVO3D_DEPHASE; ++i) __builtin_amdgcn_s_sleep(32);
-  }
-#endif
   Drone S;
   S.x = S.y = S.z = S.vx = S.vy = S.vz = 0.0; S.r = 0.2; S.prio = 5;
   if (PAD && d >= Nr) {

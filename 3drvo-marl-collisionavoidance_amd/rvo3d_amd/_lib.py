@@ -118,6 +118,11 @@ SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_reset",
            "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
 
+# the symbols that return a byte count (int64, negative: shape not supported); every other one but
+# rvo3d_last_error returns an int32 (a status, or the version)
+INT64_SYMBOLS = ("rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_x3_blob_bytes",
+                 "rvo3d_policy_rnn_tiles_blob_bytes", "rvo3d_policy_rnn_tiles_work_bytes")
+
 _lib = None
 
 
@@ -145,12 +150,10 @@ def lib():
     L.rvo3d_set_reward_f64.argtypes = [vp, vp]
     L.rvo3d_policy_sample.argtypes = [C.POINTER(PolicyHeads), C.c_int64, C.c_float, C.c_uint64, C.c_uint64] + [vp] * 6
     L.rvo3d_policy_mlp_blob_bytes.argtypes = [i32]
-    L.rvo3d_policy_mlp_blob_bytes.restype = C.c_int64
     L.rvo3d_policy_mlp_pack.argtypes = [C.POINTER(MlpWeights), C.POINTER(MlpWeights), i32, vp, vp]
     L.rvo3d_policy_mlp_sample.argtypes = [vp, i32, vp, C.c_int64, C.c_int64, vp, i32, i32, i32, vp, C.c_float,
                                           C.c_uint64, C.c_uint64] + [vp] * 6
     L.rvo3d_policy_mlp_x3_blob_bytes.argtypes = [i32]
-    L.rvo3d_policy_mlp_x3_blob_bytes.restype = C.c_int64
     L.rvo3d_policy_mlp_x3_pack.argtypes = L.rvo3d_policy_mlp_pack.argtypes
     L.rvo3d_policy_mlp_x3_sample.argtypes = L.rvo3d_policy_mlp_sample.argtypes
     L.rvo3d_reader_zero_features.argtypes = [vp, C.c_int64, C.c_int64, i32, i32, vp, vp, C.c_float, C.c_float, C.c_float,
@@ -158,10 +161,8 @@ def lib():
     L.rvo3d_policy_rows.argtypes = [C.POINTER(RnnPolicy), vp, C.c_int64, vp, vp, vp, vp, i32, vp, C.c_float, C.c_uint64,
                                     C.c_uint64, vp, vp, vp, vp]
     L.rvo3d_policy_rnn_tiles_blob_bytes.argtypes = [i32, i32, i32, i32]
-    L.rvo3d_policy_rnn_tiles_blob_bytes.restype = C.c_int64
     L.rvo3d_policy_rnn_tiles_pack.argtypes = [C.POINTER(RnnPolicy), vp, C.c_int64, vp]
     L.rvo3d_policy_rnn_tiles_work_bytes.argtypes = [C.c_int64, i32]
-    L.rvo3d_policy_rnn_tiles_work_bytes.restype = C.c_int64
     L.rvo3d_policy_rnn_tiles.argtypes = [vp, C.c_int64, i32, i32, i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64,
                                          i32, i32, vp, C.c_float, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
     L.rvo3d_reader_first_step.argtypes = [C.POINTER(GruReader), vp, C.c_int64, C.c_int64, vp, i32, C.c_int64, vp]
@@ -179,12 +180,9 @@ def lib():
     if hasattr(L, "rvo3d_debug_stamps"):  # the diagnostics build (tools/diaglib.py) only
         L.rvo3d_debug_stamps.argtypes = [vp, vp]
         L.rvo3d_debug_stamps.restype = i32
-    L.rvo3d_version.restype = i32
-    L.rvo3d_last_error.restype = C.c_char_p
     for s in SYMBOLS:
-        if s not in ("rvo3d_version", "rvo3d_last_error", "rvo3d_policy_rnn_tiles_blob_bytes",
-                     "rvo3d_policy_rnn_tiles_work_bytes"):
-            getattr(L, s).restype = i32
+        getattr(L, s).restype = C.c_int64 if s in INT64_SYMBOLS else i32
+    L.rvo3d_last_error.restype = C.c_char_p
     _lib = L
     return L
 

@@ -1,0 +1,27 @@
+"""What the host derives for an env handle (csrc/rvo3d_host_setup.hpp: thresholds, float32 error bands, launch
+geometry, zero-fill tables, building grid, staged world) against properties stated from first principles.
+
+The checks are C++: tests/host/host_setup_check.hip is a stand-alone program that calls the header's functions and
+no HIP function.  It is built here with AddressSanitizer and UndefinedBehaviorSanitizer on the host side and run as
+a child process; no GPU is needed."""
+import os
+import shutil
+import subprocess
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "3drvo-marl-collisionavoidance_amd", "csrc")
+SRC = os.path.join(ROOT, "tests", "host", "host_setup_check.hip")
+FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-O1",
+         "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"]
+
+
+def test_host_setup_properties_under_sanitizers(tmp_path):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = str(tmp_path / "host_setup_check")
+    subprocess.check_call([hipcc] + FLAGS + ["-I", CSRC, "-o", exe, SRC])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    print(res.stdout)
+    print(res.stderr)
+    assert res.returncode == 0, res.stderr[-4000:]
+    assert "host set-up ok" in res.stdout
