@@ -491,18 +491,46 @@ int rvo3d_reset_drones(rvo3d_env* h, const uint8_t* drone_mask, void* stream) {
   RVO3D_API_END
 }
 
+// The observation launch of rvo3d_observe and rvo3d_observe_envs (the device is current, the pointers are checked).
+static int observe_launch(rvo3d_env* h, float* obs, int32_t* vo_count, void* stream) {
+  Params P = h->P;
+  P.obs = obs; P.vo_count = vo_count;
+  P.zf16 = (h->cold.zf_q != 0 && (reinterpret_cast<uintptr_t>(obs) & 15) == 0 && P.nm > 0) ? 1 : 0;
+  const int rc = launch<rvo3d::kObserve>(h, P, static_cast<hipStream_t>(stream));
+  if (rc == RVO3D_OK) h->dv_valid = h->g_valid = true;  // observe files des_vel and the stage-G words
+  return rc;
+}
+
 int rvo3d_observe(rvo3d_env* h, float* obs, int32_t* vo_count, void* stream) {
   RVO3D_API_BEGIN
   DeviceGuard dg;
   int rc = check(h, true, dg);
   if (rc) return rc;
   if (!obs || !vo_count) return fail(RVO3D_ERR_INVALID, "obs / vo_count are required");
-  Params P = h->P;
-  P.obs = obs; P.vo_count = vo_count;
-  P.zf16 = (h->cold.zf_q != 0 && (reinterpret_cast<uintptr_t>(obs) & 15) == 0 && P.nm > 0) ? 1 : 0;
-  rc = launch<rvo3d::kObserve>(h, P, static_cast<hipStream_t>(stream));
-  if (rc == RVO3D_OK) h->dv_valid = h->g_valid = true;  // observe files des_vel and the stage-G words
-  return rc;
+  return observe_launch(h, obs, vo_count, stream);
+  RVO3D_API_END
+}
+
+int rvo3d_observe_envs(rvo3d_env* h, const uint8_t* env_mask, float* obs, int32_t* vo_count, float* scratch_obs,
+                       int32_t* scratch_cnt, void* stream) {
+  RVO3D_API_BEGIN
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!env_mask || !obs || !vo_count || !scratch_obs || !scratch_cnt)
+    return fail(RVO3D_ERR_INVALID, "env_mask / obs / vo_count / scratch_obs / scratch_cnt are required");
+  if (scratch_obs == obs || scratch_cnt == vo_count)
+    return fail(RVO3D_ERR_INVALID, "the scratch pair must be storage of its own");
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  rc = observe_launch(h, scratch_obs, scratch_cnt, stream);
+  if (rc) return rc;
+  const Params& P = h->P;
+  const unsigned threads = (int64_t)P.N * P.W <= 256 ? 64u : 256u;
+  hipLaunchKernelGGL(rvo3d::observe_select_kernel, dim3((unsigned)P.E), dim3(threads), 0, static_cast<hipStream_t>(stream),
+                     P.N, P.W, env_mask, reinterpret_cast<const uint32_t*>(scratch_obs), scratch_cnt,
+                     reinterpret_cast<uint32_t*>(obs), vo_count);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
   RVO3D_API_END
 }
 
@@ -849,6 +877,46 @@ int rvo3d_gae(const float* rew, const float* val, const uint8_t* cut, int64_t st
   rvo3d::GaeArgs A{rew, val, cut, steps, envs, drones, gamma, gamma * lam, adv, ret};
   hipLaunchKernelGGL(rvo3d::gae_kernel, dim3((unsigned)((columns + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_eval_action(rvo3d_env* h, const float* a, float acceler_vel, double* action64, void* stream) {
+  RVO3D_API_BEGIN
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!a || !action64) return fail(RVO3D_ERR_INVALID, "a / action64 are required");
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const size_t EN = (size_t)h->P.E * h->P.N;
+  hipLaunchKernelGGL(rvo3d::eval_action_kernel, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), h->P, a, acceler_vel, action64);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_eval_account(rvo3d_env* h, const float* reward, const uint8_t* done, const uint8_t* info, const uint8_t* finish,
+                       int32_t max_ep_len, int32_t quota, int64_t step, const rvo3d_eval_bufs* b, void* stream) {
+  RVO3D_API_BEGIN
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!reward || !done || !info || !finish || !b) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (!b->ep_len || !b->ep_ret || !b->speed_sum || !b->counted || !b->rec_len || !b->rec_ret || !b->rec_speed ||
+      !b->rec_step || !b->rec_flags || !b->remaining || !b->ended)
+    return fail(RVO3D_ERR_INVALID, "null pointer in rvo3d_eval_bufs");
+  if (max_ep_len < 1 || quota < 1) return fail(RVO3D_ERR_INVALID, "need max_ep_len >= 1 and quota >= 1");
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const rvo3d::EvalAccountArgs A{reward, done, info, finish, max_ep_len, quota, step, b->ep_len, b->ep_ret, b->speed_sum,
+                                 b->counted, b->rec_len, b->rec_ret, b->rec_speed, b->rec_step, b->rec_flags, b->remaining,
+                                 b->ended};
+  // eval_lanes_per_env(N) lanes per env: up to 256 envs per workgroup for N = 1, one wave per env from 33 drones on
+  const size_t lanes = (size_t)h->P.E * (size_t)rvo3d::eval_lanes_per_env(h->P.N);
+  hipLaunchKernelGGL(rvo3d::eval_account_kernel,
+                     dim3((unsigned)((lanes + rvo3d::kEvalAccountThreads - 1) / rvo3d::kEvalAccountThreads)),
+                     dim3(rvo3d::kEvalAccountThreads), 0, static_cast<hipStream_t>(stream), h->P, A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END

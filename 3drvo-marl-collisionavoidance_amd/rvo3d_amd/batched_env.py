@@ -202,6 +202,39 @@ class BatchedDroneEnv:
             self._obs_ver = self._own_versions()
         return o, c
 
+    def observe_envs(self, env_mask):
+        """observe() for the envs whose mask byte is non-zero (rvo3d_observe_envs): their rows of the env's own obs /
+        vo_count are rewritten, the other envs keep the observation of their last step.  env_mask: [E] bytes / bools."""
+        m = torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+        if tuple(m.shape) != (self.E,):
+            raise AssertionError(f"env_mask must have shape ({self.E},)")
+        if getattr(self, "_scratch", None) is None:
+            self._scratch = (torch.zeros_like(self.obs), torch.zeros_like(self.vo_count))
+        so, sc = self._scratch
+        # rows are copied whole from a full observation: a consistent pair stays one (see _call_step)
+        keep = self._obs_ver is not None and self._obs_ver == self._own_versions()
+        self._obs_ver = None
+        _lib.check(_lib.lib().rvo3d_observe_envs(self._h, _ptr(m), _ptr(self.obs), _ptr(self.vo_count), _ptr(so), _ptr(sc),
+                                                 self._stream()), "rvo3d_observe_envs")
+        if keep:
+            self._obs_ver = self._own_versions()
+        self._keep = m
+        return self.obs, self.vo_count
+
+    def eval_action(self, a, acceler_vel: float = 1.0):
+        """The evaluator's glue (post_train.py:63-74) on the device: acceler_vel * round(a, 2) + vel in numpy's own
+        types, not rounded again (rvo3d_eval_action).  a: float32 [E, N, 3].  Returns the env's persistent float64
+        [E, N, 3] action buffer, overwritten by the next call."""
+        a = torch.as_tensor(a, device=self.device).to(torch.float32).contiguous()
+        if tuple(a.shape) != (self.E, self.N, 3):
+            raise AssertionError(f"a must have shape ({self.E}, {self.N}, 3)")
+        if getattr(self, "_action64", None) is None:
+            self._action64 = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
+        _lib.check(_lib.lib().rvo3d_eval_action(self._h, _ptr(a), float(acceler_vel), _ptr(self._action64),
+                                                self._stream()), "rvo3d_eval_action")
+        self._keep_a = a
+        return self._action64
+
     def des_vel(self):
         out = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
         _lib.check(_lib.lib().rvo3d_des_vel(self._h, _ptr(out), self._stream()), "rvo3d_des_vel")

@@ -20,16 +20,77 @@ those E * ceil(num_episodes / E) episodes; E = 1 is the reference's sequential l
 (pinned by tests/golden/post_train_*.npz, produced by the reference's policy_test itself).
 A "math domain error" (env_train=False: the reference's evaluator aborts when two drones
 approach inside r + mr, vel_obs3D.py:13) is raised at the end of the step it happens in.
+
+fused=True (opt-in) keeps the whole step on the device and the host out of the episode: policy ->
+rvo3d_eval_action (the glue above, one kernel) -> the plain env step -> rvo3d_eval_account (the
+bookkeeping above for every env, finished episodes recorded on the device) -> reset of the envs
+that ended -> rvo3d_observe_envs (ONLY those envs are re-observed).  The host reads one counter
+(and, with env_train=False, the error word) every `poll_every` steps; an error is raised at that
+poll - also one of the at most poll_every - 1 uncounted steps behind the last record.  The
+records are sorted by (step, env) - the order in which the loop above appends - and go through
+`summarize_records`.  Per env this is the reference's loop exactly: an env in mid-episode keeps
+the observation of its step (ir_gym.observation_reward, with the action).  The unfused loop
+re-observes EVERY env with action = 0 (ir_gym.env_observation) whenever any env ended, so with
+E > 1 and a policy that looks at its observation an env's trajectory there depends on its
+neighbours' episode ends; with E = 1 the two loops agree.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 import torch
 
+from .. import _lib
+
+# bits of a record's flag byte (rvo3d_eval_account)
+REC_ARRIVED, REC_FINISHED, REC_COLLIDED, REC_TIMEOUT = 1, 2, 4, 8
+
+
+def summarize_records(step, env, length, ret, speed, flags, policy_name="policy"):
+    """The evaluation's result from its episode records (plain numpy arrays, one entry per counted
+    episode, any order): sorted by (step, env) - the order in which the sequential loop meets them -
+    they give the returned dict, the result line and the per-episode lines of `inf_print`
+    (post_train.py:89-128).  Returns (result, line, episode_lines)."""
+    step, env = np.asarray(step), np.asarray(env)
+    order = np.lexsort((env, step))
+    length = np.asarray(length)[order]
+    ret = np.asarray(ret, dtype=np.float64)[order]
+    speed = np.asarray(speed, dtype=np.float64)[order]
+    flags = np.asarray(flags)[order].astype(np.int64)
+    arrived = (flags & REC_ARRIVED) != 0
+    total = len(order)
+    sn = int(((flags & REC_FINISHED) != 0).sum())
+    ep_len_list = [int(x) for x in length[arrived]]
+    mean_speed_list = [float(x) for x in speed]
+    ep_ret_list = [float(x) for x in ret]
+    episode_lines = ["%s, Episode %d \t EpRet %.3f \t EpLen %d \t EpSpeed  %.3f"
+                     % ("Successful" if arrived[n] else "Fail", n, ret[n], length[n], speed[n]) for n in range(total)]
+    mean_len = 0 if not ep_len_list else np.round(np.mean(ep_len_list), 2)
+    std_len = 0 if not ep_len_list else np.round(np.std(ep_len_list), 2)
+    average_speed = np.round(np.mean(mean_speed_list), 2)
+    std_speed = np.round(np.std(mean_speed_list), 2)
+    line = ("policy_name: " + policy_name + "  successful rate: {:.2%}".format(sn / total)
+            + " average EpLen: %s std length %s average speed: %s std speed %s"
+            % (mean_len, std_len, average_speed, std_speed))
+    result = dict(success_rate=sn / total, mean_len=float(mean_len), std_len=float(std_len),
+                  average_speed=float(average_speed), std_speed=float(std_speed),
+                  episodes=total, ep_ret=ep_ret_list, ep_len=ep_len_list, speed=mean_speed_list)
+    return result, line, episode_lines
+
 
 class post_train:
     def __init__(self, env, num_episodes=100, max_ep_len=150, acceler_vel=1.0, render=False,
-                 save=False, neighbor_region=4, neighbor_num=5, args=None, **kwargs):
+                 save=False, neighbor_region=4, neighbor_num=5, args=None, fused=False, policy_kernel=None,
+                 poll_every=8, seed=0, **kwargs):
+        """fused: the device-side loop (module docstring); policy_kernel: None (policy.step_tensors), "mlp"
+        (rvo3d_policy_mlp_sample) or "mlp_x3" (rvo3d_policy_mlp_x3_sample) - either loop; poll_every: steps between
+        two host reads of the fused loop; seed: of the kernels' counter-based noise."""
+        if policy_kernel not in (None, "mlp", "mlp_x3"):
+            raise ValueError(f"policy_kernel must be None, 'mlp' or 'mlp_x3', not {policy_kernel!r}")
+        if int(poll_every) < 1:
+            raise ValueError("poll_every must be >= 1")
+        self.fused, self.policy_kernel, self.poll_every, self.seed = bool(fused), policy_kernel, int(poll_every), int(seed)
         self.env = env
         self.num_episodes = num_episodes
         self.max_ep_len = max_ep_len
@@ -55,10 +116,41 @@ class post_train:
             ac.load_state_dict(ck["model_state"], strict=True)
             policy = ac
         policy.eval()
+        if self.policy_kernel is not None:
+            return self._kernel_policy(policy, std_factor)
 
         def get_action(obs, cnt):  # batched model.act(x, std_factor), stays on the device
             a, _, _ = policy.step_tensors((obs, cnt), std_factor)
             return a.float()
+
+        return get_action
+
+    def _kernel_policy(self, policy, std_factor):
+        """model.act as ONE kernel (policy_kernel "mlp": bf16 products, "mlp_x3": float32-class), on the packed
+        weights of `policy.mlp_blob`; noise from (seed, number of calls so far)."""
+        env = self.env
+        precision = "bf16" if self.policy_kernel == "mlp" else "x3"
+        blob_of = getattr(policy, "mlp_blob", None)
+        if blob_of is None or blob_of(precision) is None or getattr(policy, "obs_width", None) != env.W:
+            raise ValueError(f"policy_kernel={self.policy_kernel!r} needs an MLP(256, 256) actor-critic on the env's "
+                             "observation width (mlp_ac.mlp_blob returns its packed weights)")
+        L = _lib.lib()
+        fn = L.rvo3d_policy_mlp_sample if self.policy_kernel == "mlp" else L.rvo3d_policy_mlp_x3_sample
+        rows = env.E * env.N
+        act = torch.empty((rows, 3), dtype=torch.float32, device=env.device)
+        logp = torch.empty(rows, dtype=torch.float32, device=env.device)   # scratch
+        val = torch.empty(rows, dtype=torch.float32, device=env.device)    # scratch
+        calls = [0]
+        p = lambda t: C.c_void_p(t.data_ptr())
+
+        def get_action(obs, cnt):
+            mb = blob_of(precision)   # (cached; repacked when a parameter changed)
+            log_std = policy.log_std
+            _lib.check(fn(p(mb["blob"]), env.W, p(obs), obs.stride(0), rows, p(cnt), 12, 9, 1 if mb["tanh"] else 0,
+                          p(log_std), float(std_factor), self.seed, calls[0], p(act), p(logp), p(val), None, None,
+                          C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)), "rvo3d_policy_mlp_sample")
+            calls[0] += 1
+            return act
 
         return get_action
 
@@ -71,6 +163,8 @@ class post_train:
         if policy_type == "drl":
             act_fn = self.load_policy(policy if policy is not None else policy_path,
                                       self.std_factor, policy_dict=policy_dict)
+        if self.fused:
+            return self._policy_test_fused(act_fn, policy_name, result_path, result_name)
         env.reset()
         obs, cnt = env.observe()
         ep_len = torch.zeros(E, dtype=torch.int64, device=dev)
@@ -147,3 +241,59 @@ class post_train:
         return dict(success_rate=sn / total, mean_len=float(mean_len), std_len=float(std_len),
                     average_speed=float(average_speed), std_speed=float(std_speed),
                     episodes=n, ep_ret=ep_ret_list, ep_len=ep_len_list, speed=mean_speed_list)
+
+    def _policy_test_fused(self, act_fn, policy_name, result_path, result_name):
+        """The same evaluation with the episodes accounted for on the device (module docstring)."""
+        env = self.env
+        E, N, dev = env.E, env.N, env.device
+        quota = -(-self.num_episodes // E)   # episodes counted per env
+        total = quota * E
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        t = dict(ep_len=z(E, torch.int32), ep_ret=z(E, torch.float64), speed_sum=z(E, torch.float64),
+                 counted=z(E, torch.int32), rec_len=z((E, quota), torch.int32), rec_ret=z((E, quota), torch.float64),
+                 rec_speed=z((E, quota), torch.float64), rec_step=z((E, quota), torch.int64),
+                 rec_flags=z((E, quota), torch.uint8), remaining=torch.full((1,), total, dtype=torch.int32, device=dev),
+                 ended=z(E, torch.uint8))
+        bufs = _lib.EvalBufs(**{k: v.data_ptr() for k, v in t.items()})
+        L = _lib.lib()
+        p = lambda x: C.c_void_p(x.data_ptr())
+        check_domain = not getattr(env, "env_train", True)
+        env.reset()
+        obs, cnt = env.observe()
+        step = 0
+        while True:
+            if act_fn is not None:
+                a = act_fn(obs.view(-1, env.W), cnt.view(-1)).view(E, N, 3)
+                action = env.eval_action(a, self.acceler_vel)
+            else:
+                action = env.des_vel()
+            obs, cnt, rew, done, info, fin = env.step(action)             # plain drone_step
+            _lib.check(L.rvo3d_eval_account(env._h, p(rew), p(done), p(info), p(fin), self.max_ep_len, quota, step,
+                                            C.byref(bufs), env._stream()), "rvo3d_eval_account")
+            env.reset(t["ended"])
+            obs, cnt = env.observe_envs(t["ended"])
+            step += 1
+            if step % self.poll_every == 0:
+                if check_domain:
+                    flags = env.error_flags()   # (read-and-clear; both bits are acted on here)
+                    if flags & 2:
+                        raise ValueError("math domain error")
+                    if flags & 1:
+                        raise ValueError("observation contains NaN/Inf")
+                if int(t["remaining"].item()) <= 0:
+                    break
+        e_idx = np.repeat(np.arange(E), quota)   # env of record [e][k]; remaining <= 0: every slot is filled
+        # the records as the device left them, [E][quota] each (kept for the caller: self.records)
+        rec = self.records = {k: t[k].cpu().numpy() for k in ("rec_step", "rec_len", "rec_ret", "rec_speed", "rec_flags")}
+        flat = {k: v.reshape(-1) for k, v in rec.items()}
+        result, line, episode_lines = summarize_records(flat["rec_step"], e_idx, flat["rec_len"], flat["rec_ret"],
+                                                        flat["rec_speed"], flat["rec_flags"], policy_name)
+        if self.inf_print:
+            for ln in episode_lines:
+                print(ln)
+        if result_path is not None:
+            with open(result_path + result_name, "a") as f:
+                print(line, file=f)
+        if self.inf_print:
+            print(line)
+        return result

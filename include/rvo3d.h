@@ -350,6 +350,52 @@ int rvo3d_rollout_account(int32_t num_envs, int32_t num_drones, const float *rew
 int rvo3d_gae(const float *rew, const float *val, const uint8_t *cut, int64_t steps, int64_t envs, int64_t drones,
               double gamma, double lam, float *adv, float *ret, void *stream);
 
+/* ---- the evaluator's per-step glue around the env step (train/policy/post_train.py:38-128), handle-bound: nothing here
+ * synchronises or allocates, every argument check runs before the first HIP call ---- */
+
+/* The evaluator's action (post_train.py:63-74) in numpy's own types: r = rint(a * 100f) / 100f (np.round(a, 2) in
+ * float32, a true division), action = (double)(acceler_vel * r) + vel (float32 product widened, float64 sum; unlike
+ * rvo3d_step_policy NOT rounded again).  a [E][N][3] float32, action64 [E][N][3] float64 (what rvo3d_step then takes as
+ * RVO3D_F64); vel is the handle's own state. */
+int rvo3d_eval_action(rvo3d_env *h, const float *a, float acceler_vel, double *action64, void *stream);
+
+/* The episode bookkeeping of post_train.policy_test (:78-105) for every env, after the step and before any reset.
+ * Per env: speed = (sum over its drones of sqrt(vx^2 + vy^2 + vz^2)) / N from the handle's post-step velocities, in
+ * float64 and in a fixed order (bit-reproducible); speed_sum += speed; ep_ret += (double)reward[e][0]; len = ep_len + 1;
+ * the episode ended = any(done) || len == max_ep_len || all(finish)  (==: the trainer's timeout is >).  An env that ended
+ * with counted[e] < quota stores the record [e][counted[e]] - len, ep_ret, speed_sum / len, step, flags (1 = all info,
+ * 2 = all finish, 4 = any done, 8 = timeout) -, counts it and takes one off *remaining (atomic).  An env that ended has
+ * its three running values zeroed, any other stores len; ended[e] = 1 / 0 is written for every env (the mask for
+ * rvo3d_reset and rvo3d_observe_envs).  An env past its quota goes on, unrecorded.
+ * bufs: HOST struct of device pointers; the running values [E] are zero before the first call, the records [E][quota],
+ * remaining [1] set to E * quota by the caller.  reward [E][N] float32, done / info / finish [E][N] bytes (the step's
+ * outputs); max_ep_len >= 1, quota >= 1, step: the caller's step number. */
+typedef struct rvo3d_eval_bufs {
+  int32_t *ep_len;     /* [E] running                                       */
+  double *ep_ret;      /* [E]                                               */
+  double *speed_sum;   /* [E]                                               */
+  int32_t *counted;    /* [E] records of this env so far                    */
+  int32_t *rec_len;    /* [E][quota] records                                */
+  double *rec_ret;
+  double *rec_speed;
+  int64_t *rec_step;
+  uint8_t *rec_flags;
+  int32_t *remaining;  /* [1]                                               */
+  uint8_t *ended;      /* [E] written in full by every call                 */
+} rvo3d_eval_bufs;
+int rvo3d_eval_account(rvo3d_env *h, const float *reward, const uint8_t *done, const uint8_t *info,
+                       const uint8_t *finish, int32_t max_ep_len, int32_t quota, int64_t step,
+                       const rvo3d_eval_bufs *bufs, void *stream);
+
+/* rvo3d_observe for the envs whose mask byte is non-zero (env_mask [E], required): their rows of obs / vo_count receive
+ * bit for bit what rvo3d_observe writes, the other envs' rows are not written at all - an env in mid-episode keeps the
+ * observation of its step (ir_gym.observation_reward, with the action), as in the reference, which observes with
+ * action = 0 only behind a reset.  Implemented as the full observation into the caller's scratch pair (scratch_obs /
+ * scratch_cnt: the shapes of obs / vo_count, distinct from them) and a row select, so the handle's derived state
+ * (des_vel on file, stage-G words, max_dev) is what rvo3d_observe leaves. */
+int rvo3d_observe_envs(rvo3d_env *h, const uint8_t *env_mask, float *obs, int32_t *vo_count, float *scratch_obs,
+                       int32_t *scratch_cnt, void *stream);
+
 /* mdin.drone_step returns its rewards as Python floats (mdin.py:28: rvo_reward + mov_reward in
  * float64).  Attach a device buffer reward64 [E][N] and every following step (all three step
  * entry points) also writes the float64 value next to the float32 one; NULL detaches.  The
