@@ -22,8 +22,8 @@ __global__ void reset_kernel(const Params P, const uint8_t* env_mask, const uint
   P.real_len()[g] = 0.0; P.max_dev()[g] = 0.0; P.yaw()[g] = 0.0; P.pitch()[g] = 0.0;
   double c1[3];
   load_wp(P, g, 1, c1);
-  RVO3D_STORE_CUR(P, g, c1);
-  RVO3D_STORE_PREV(P, g, s);
+  store3(P.cur(0), P.cur(1), P.cur(2), g, c1);
+  store3(P.prev(0), P.prev(1), P.prev(2), g, s);
   // des_vel of the start state is on file; a start state with a non-zero deviation (only
   // with non-finite waypoints) is left to the step's own dronestate
   const bool plain = P.dev0()[g] == 0.0;
@@ -40,9 +40,9 @@ __global__ void wpcache_kernel(const Params P) {
   i = i < 1 ? 1 : (i > np - 1 ? np - 1 : i);  // the clamp only guards the table lookup
   double v[3];
   load_wp(P, g, i, v);
-  RVO3D_STORE_CUR(P, g, v);
+  store3(P.cur(0), P.cur(1), P.cur(2), g, v);
   load_wp(P, g, i - 1, v);
-  RVO3D_STORE_PREV(P, g, v);
+  store3(P.prev(0), P.prev(1), P.prev(2), g, v);
 }
 
 // rvo3d_load_world: dronestate of every drone's reset state (drone.py:254-263 after
@@ -64,7 +64,7 @@ __global__ void des_vel_kernel(const Params P, double* out) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= P.E * P.N) return;
   double p[3] = {P.px()[g], P.py()[g], P.pz()[g]}, cur[3], dv[3];
-  RVO3D_LOAD_CUR(P, g, cur);
+  load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
   des_vel(P, p, cur, dv);
   out[3 * (size_t)g] = dv[0]; out[3 * (size_t)g + 1] = dv[1]; out[3 * (size_t)g + 2] = dv[2];
 }
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(512) rvo_vel_kernel(const Params P, const RvoV
   __syncthreads();
   if (!active) return;
   double cur[3], des[3];
-  RVO3D_LOAD_CUR(P, g, cur);
+  load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
   const double p[3] = {S.x, S.y, S.z}, v0[3] = {S.vx, S.vy, S.vz};
   des_vel(P, p, cur, des);
   double lo[3];

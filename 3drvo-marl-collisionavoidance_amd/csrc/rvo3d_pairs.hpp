@@ -395,8 +395,13 @@ template <> struct OffsetSet<4> {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
+__device__ __forceinline__ v2f ld2(const float* a, int i0, int i1) { return (v2f){a[i0], a[i1]}; }
 // One end of two candidate pairs as stage X1 reads it from the fp32 image (two pairs per trip in packed fp32).
-struct X1End { v2f x, y, z, r, vx, vy, vz, kd, prio; };
+struct X1End { v2f x, y, z, r, vx, vy, vz, kd, prio; };  // (x y z r: doubled arrays, slots a0 a1; the rest: single copy, s0 s1)
+__device__ __forceinline__ X1End x1_end(const Lds& L, int a0, int a1, int s0, int s1) {
+  return {ld2(L.w[WX], a0, a1), ld2(L.w[WY], a0, a1), ld2(L.w[WZ], a0, a1), ld2(L.w[WR], a0, a1), ld2(L.w[WVX], s0, s1),
+          ld2(L.w[WVY], s0, s1), ld2(L.w[WVZ], s0, s1), ld2(L.w[WKD], s0, s1), ld2(L.w[WPRIO], s0, s1)};
+}
 // Stage X1's verdicts for the two pairs: request the exact stage for the owner (pi) / the neighbour (pj); somebody
 // possibly approaches (keep, ROWS: the pair stays in the word filed for the next sweep A).
 struct X1Bits { bool pi0, pj0, pi1, pj1, keep0, keep1; };
@@ -530,20 +535,15 @@ __device__ __forceinline__ bool x1_queue(const Params& P, const Lds& L, int lane
     X1Bits b;
     {
       const X1Idx k(e, N);
-#define RVO3D_LD2(K, F) ((v2f){L.w[K][k.F##0], L.w[K][k.F##1]})
-      const X1End me = {RVO3D_LD2(WX, oa), RVO3D_LD2(WY, oa), RVO3D_LD2(WZ, oa), RVO3D_LD2(WR, oa), RVO3D_LD2(WVX, s),
-                        RVO3D_LD2(WVY, s), RVO3D_LD2(WVZ, s), RVO3D_LD2(WKD, s), RVO3D_LD2(WPRIO, s)};
-      const X1End o = {RVO3D_LD2(WX, ob), RVO3D_LD2(WY, ob), RVO3D_LD2(WZ, ob), RVO3D_LD2(WR, ob), RVO3D_LD2(WVX, j),
-                       RVO3D_LD2(WVY, j), RVO3D_LD2(WVZ, j), RVO3D_LD2(WKD, j), RVO3D_LD2(WPRIO, j)};
+      const X1End me = x1_end(L, k.oa0, k.oa1, k.s0, k.s1), o = x1_end(L, k.ob0, k.ob1, k.j0, k.j1);
       const v2f z2 = {0.f, 0.f};
       if (zero) {
         b = x1_pairs<TOUCH, true>(P, false, me, o, z2, z2, z2, z2, z2, z2);
       } else {
         const v2f four2 = {4.f, 4.f};
-        b = x1_pairs<TOUCH, false>(P, false, me, o, four2 * RVO3D_LD2(WAX, s), four2 * RVO3D_LD2(WAY, s),
-                                   four2 * RVO3D_LD2(WAZ, s), RVO3D_LD2(WAX, j), RVO3D_LD2(WAY, j), RVO3D_LD2(WAZ, j));
+        b = x1_pairs<TOUCH, false>(P, false, me, o, four2 * ld2(L.w[WAX], k.s0, k.s1), four2 * ld2(L.w[WAY], k.s0, k.s1),
+                                   four2 * ld2(L.w[WAZ], k.s0, k.s1), ld2(L.w[WAX], k.j0, k.j1), ld2(L.w[WAY], k.j0, k.j1), ld2(L.w[WAZ], k.j0, k.j1));
       }
-#undef RVO3D_LD2
     }
     // (several envs per wave: the slots are decoded again for the verdicts rather than carried - ten registers -
     // across the arithmetic; the entry made opaque, or the compiler carries them all the same)
@@ -559,6 +559,29 @@ __device__ __forceinline__ bool x1_queue(const Params& P, const Lds& L, int lane
     }
   }
   return true;
+}
+
+// Stage X2: pair_eval of the pairs requested from this lane (LDS masks; one wave: also its own m2r).  Returns kept.
+template <int NW, bool ROWS, bool TOUCH, bool TRAIN>
+__device__ __forceinline__ int exact_stage(const Params& P, const Lds& L, int lane, int lbase, int g, const Drone& S, const double a[3],
+                                           unsigned long long m2r, bool& flag, double& tmin, bool& collision) {
+  int kept = 0;
+#pragma unroll  // (a rolled loop over the words is smaller but 4 % slower at 128 and 256 drones)
+  for (int w = 0; w < NW; ++w) {
+    unsigned long long m2 = L.mask2[mi<NW>(L, lane, w)] | (w == 0 ? m2r : 0ull);
+    while (m2) {
+      const int j = 64 * w + __builtin_ctzll(m2);
+      m2 &= m2 - 1;
+      const PairOut po = pair_eval<TRAIN>(P, S, L, lbase + j, a);
+      if (TOUCH && po.collision) collision = true;
+      if (po.flag) {
+        flag = true;
+        if (po.t < tmin) tmin = po.t;
+        if (ROWS && P.nm > 0) kept = insert_row(P, L, g, lbase, S, po, j, kept);
+      }
+    }
+  }
+  return kept;
 }
 
 // Symmetric sweep: every unordered pair {i, j} of an env is examined once, by the
@@ -678,15 +701,11 @@ __device__ __forceinline__ int sweep_env(const Params& P, const Lds& L, int lane
         if (jd0 >= N) jd0 -= N;
         if (jd1 >= N) jd1 -= N;
         const int ja = el * N + jd0, jb = el * N + jd1;  // slots in the single-copy arrays
-#define RVO3D_LD2(K, i0, i1) ((v2f){L.w[K][i0], L.w[K][i1]})
-        const X1End o = {RVO3D_LD2(WX, oa, ob), RVO3D_LD2(WY, oa, ob), RVO3D_LD2(WZ, oa, ob),
-                         RVO3D_LD2(WR, oa, ob), RVO3D_LD2(WVX, ja, jb), RVO3D_LD2(WVY, ja, jb),
-                         RVO3D_LD2(WVZ, ja, jb), RVO3D_LD2(WKD, ja, jb), RVO3D_LD2(WPRIO, ja, jb)};
+        const X1End o = x1_end(L, oa, ob, ja, jb);
         const v2f z2 = {0.f, 0.f};
-        const v2f ajx = zero_act ? z2 : RVO3D_LD2(WAX, ja, jb),
-                  ajy = zero_act ? z2 : RVO3D_LD2(WAY, ja, jb),
-                  ajz = zero_act ? z2 : RVO3D_LD2(WAZ, ja, jb);
-#undef RVO3D_LD2
+        const v2f ajx = zero_act ? z2 : ld2(L.w[WAX], ja, jb),
+                  ajy = zero_act ? z2 : ld2(L.w[WAY], ja, jb),
+                  ajz = zero_act ? z2 : ld2(L.w[WAZ], ja, jb);
         const X1Bits xb = x1_pairs<TOUCH, false>(P, far, me, o, tax, tay, taz, ajx, ajy, ajz);
         bool pi0 = xb.pi0, pj0 = xb.pj0, pi1 = xb.pi1, pj1 = xb.pj1;
         if (ROWS) {
@@ -722,24 +741,7 @@ __device__ __forceinline__ int sweep_env(const Params& P, const Lds& L, int lane
     atomicMax(&P.dbg[(size_t)blockIdx.x * 32 + (ROWS ? 23 : 21)], (unsigned long long)c);
   }
 #endif
-  if (active && !RVO3D_ABLATED(32)) {
-    const int lbase = el * N;
-#pragma unroll  // (a rolled loop over the words is smaller but 4 % slower at 128 and 256 drones)
-    for (int w = 0; w < NW; ++w) {
-      unsigned long long m2 = L.mask2[mi<NW>(L, lane, w)] | (w == 0 ? m2r : 0ull);
-      while (m2) {  // stage X2: exact, requested pairs only
-        const int j = 64 * w + __builtin_ctzll(m2);
-        m2 &= m2 - 1;
-        const PairOut po = pair_eval<TRAIN>(P, S, L, lbase + j, a);
-        if (TOUCH && po.collision) collision = true;
-        if (po.flag) {
-          flag = true;
-          if (po.t < tmin) tmin = po.t;
-          if (ROWS && P.nm > 0) kept = insert_row(P, L, g, lbase, S, po, j, kept);
-        }
-      }
-    }
-  }
+  if (active && !RVO3D_ABLATED(32)) kept = exact_stage<NW, ROWS, TOUCH, TRAIN>(P, L, lane, el * N, g, S, a, m2r, flag, tmin, collision);
   if (ROWS && !TOUCH) RVO3D_STAMP(13);
   if (!ROWS) RVO3D_STAMP(15);
   return kept;

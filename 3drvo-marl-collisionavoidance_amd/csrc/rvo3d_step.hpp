@@ -1,5 +1,5 @@
 // rvo3d_step.hpp -- The environment step kernel and its per-drone parts: building gate, observation writers,
-// zero fill, rewards, env_kernel<MODE, NW>.
+// zero fill, rewards, env_kernel<MODE, NW, NFIX, TRAIN, PAD>.
 // Part of the gfx950 device code (see rvo3d_device.hpp for the overview).
 #pragma once
 
@@ -120,6 +120,9 @@ __device__ __forceinline__ void stage_row(const Params& P, const Lds& L, int tid
   if (bad) atomicOr(P.err, 1u);
 }
 
+template <int NW>  // waves of this workgroup (<= NW; T = N rounded up to 64): what the cooperative row writers stride by
+__device__ __forceinline__ int waves_of(const Lds& L) { return NW == 1 ? 1 : (L.T >> 6); }
+
 // 16-B row writer, part 2 (W even, obs 16-B aligned).  Two consecutive rows (an even row and
 // its successor, counted over the whole obs tensor) are 2 * W * 4 = 16 * q bytes starting on a
 // 16-B boundary: q = W / 2 chunks of 16 B.  One wave-instruction stores one row pair: lane c
@@ -133,7 +136,7 @@ __device__ __forceinline__ void row_fill_pairs(const Params& P, const Lds& L, in
                                                int nrows) {
   const int q = P.W >> 1;  // 8-B units per row = 16-B chunks per row pair
   const int ln = tid & 63, wv = tid >> 6;
-  const int nwv = NW == 1 ? 1 : (L.T >> 6);  // waves of this workgroup (<= NW; T = N rounded up to 64)
+  const int nwv = waves_of<NW>(L);
   const int pair0 = row0 >> 1;
   const int npairs = ((row0 + nrows + 1) >> 1) - pair0;
   const int rbase = 2 * pair0 - row0;  // local row of the first pair's first row: 0 or -1
@@ -213,14 +216,13 @@ __device__ __forceinline__ void early_zero_blocks(const Params& P, const Lds& L,
                                                   int nrows) {
   const uint32_t rb = 4u * (uint32_t)P.W;  // row bytes (a multiple of 8)
   const int ln = tid & 63, wv = tid >> 6;
-  const int nwv = NW == 1 ? 1 : (L.T >> 6);
+  const int nwv = waves_of<NW>(L);
   (void)nrows;  // a full workgroup (two_phase_rows)
   char* const base = reinterpret_cast<char*>(P.obs) + (size_t)row0 * rb;
   const uint32_t blk = (uint32_t)wv * 16u + ((uint32_t)ln >> 2);
   typedef float v4f __attribute__((ext_vector_type(4)));
   // which trips store is a property of the thread quad, tabulated by the host (rvo3d_create): no
-  // per-trip offset arithmetic.  Streaming stores: whole 64-B blocks nobody reads back (-1 %; the
-  // windows of part 2, whose lines are shared with the kept rows, are faster as ordinary stores)
+  // per-trip offset arithmetic.  Ordinary stores, like the windows of part 2.
   const int iters = P.cold().zf_iters;
   uint32_t m = P.cold().zmask[tid >> 2];
   if (P.prev_cnt) {
@@ -265,7 +267,7 @@ __device__ __forceinline__ void late_row_windows(const Params& P, const Lds& L, 
                                                  int nrows) {
   const uint32_t rb = 4u * (uint32_t)P.W, q = rb >> 3;  // row bytes, 8-B units per row
   const int ln = tid & 63, wv = tid >> 6;
-  const int nwv = NW == 1 ? 1 : (L.T >> 6);
+  const int nwv = waves_of<NW>(L);
   const float2* pro2 = reinterpret_cast<const float2*>(L.w[0]);
   char* const base = reinterpret_cast<char*>(P.obs) + (size_t)row0 * rb;
   const int ch = ln & 7;
@@ -373,10 +375,6 @@ __device__ __forceinline__ void store3(double* const a0, double* const a1, doubl
                                        const double v[3]) {
   a0[g] = v[0]; a1[g] = v[1]; a2[g] = v[2];
 }
-#define RVO3D_LOAD_CUR(P, g, out) load3((P).cur(0), (P).cur(1), (P).cur(2), g, out)
-#define RVO3D_LOAD_PREV(P, g, out) load3((P).prev(0), (P).prev(1), (P).prev(2), g, out)
-#define RVO3D_STORE_CUR(P, g, v) store3((P).cur(0), (P).cur(1), (P).cur(2), g, v)
-#define RVO3D_STORE_PREV(P, g, v) store3((P).prev(0), (P).prev(1), (P).prev(2), g, v)
 
 // ir_gym.rvo_reward_cal (ir_gym.py:64-133), the part that does not depend on the sweep:
 // angle_punish + vel_penalty.  The sweep's safety term is added afterwards in the
@@ -445,6 +443,12 @@ __device__ __forceinline__ double mov_reward_k(const Params& P, bool collision, 
 // into the optional float64 output).
 
 enum Mode { kObserve = 0, kStep = 1, kStepAutoReset = 2 };
+
+// The old count of row g (consistent obs / vo_count pair, early_zero_blocks), clamped to nm (more only stores more).
+__device__ __forceinline__ uint32_t old_kept(const Params& P, int g) {
+  const uint32_t c = (uint32_t)P.prev_cnt[g];
+  return c < (uint32_t)P.nm ? c : (uint32_t)P.nm;
+}
 
 // 128 VGPRs = 4 waves per SIMD.  One-wave workgroups (N <= 64): the 4096 waves of 64 x 4096 are
 // all resident at once.  N <= 256 (one env per workgroup of 2 or 4 waves): the fourth wave per
@@ -524,16 +528,12 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   //      state (waypoints, des_vel, deviation) is fetched after sweep A, which needs none of it
   uint32_t gw[NW];  // candidate words (stage G): on file from the previous step if it ended in this state
   const bool have_gw = MODE != kObserve && P.g_cached != 0;
-  // the old count of this drone's row (consistent obs / vo_count pair, early_zero_blocks), clamped to nm (a
-  // larger count only makes more blocks store); read before anything of this step is stored.  One-wave
+  // the old count of this drone's row (old_kept), read before anything of this step is stored.  One-wave
   // workgroups read it here; several waves where the reset state is requested (one register less across the
   // sweeps: no spills there)
   uint32_t old_cnt = 0;
   if (active) {
-    if (LITE && NW == 1 && P.prev_cnt) {
-      old_cnt = (uint32_t)P.prev_cnt[g];
-      old_cnt = old_cnt < (uint32_t)P.nm ? old_cnt : (uint32_t)P.nm;
-    }
+    if (LITE && NW == 1 && P.prev_cnt) old_cnt = old_kept(P, g);
     S.x = P.px()[g]; S.y = P.py()[g]; S.z = P.pz()[g];
     S.vx = P.vx()[g]; S.vy = P.vy()[g]; S.vz = P.vz()[g];
     if (P.uniform_rp) { S.r = P.r0; S.prio = P.prio0; }
@@ -597,8 +597,8 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     if (active) {  // drone.dronestate (drone.py:254-263)
       double prev[3];
       max_dev = P.max_dev()[g];
-      RVO3D_LOAD_CUR(P, g, cur);
-      RVO3D_LOAD_PREV(P, g, prev);
+      load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
+      load3(P.prev(0), P.prev(1), P.prev(2), g, prev);
       const double p[3] = {S.x, S.y, S.z};
       des_vel(P, p, cur, dv);
       dev = deviation(prev, cur, p);
@@ -650,25 +650,20 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   double prev[3] = {0, 0, 0}, yaw = 0, pitch = 0, real_len = 0, route_len = 0;
   int npts = 2;
   bool f_arrive_in = false, f_dest_in = false;
-#define RVO3D_LOAD_INTEGRATION_STATE()                                               \
-  {                                                                                  \
-    wpi = P.wp_idx()[g];                                                             \
-    RVO3D_LOAD_PREV(P, g, prev);                                                     \
-    yaw = P.yaw()[g]; pitch = P.pitch()[g]; real_len = P.real_len()[g];              \
-    route_len = P.route_len()[g];                                                    \
-    npts = P.n_points()[g];                                                          \
-    f_arrive_in = P.arrive()[g] != 0; f_dest_in = P.dest()[g] != 0;                  \
-  }
   if (active) {
     max_dev = P.max_dev()[g];
-    RVO3D_LOAD_CUR(P, g, cur);
+    load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
     uint32_t dvk_a = 0, dvk_b = 0;
     if (P.dv_cached) { dvk_a = P.dvk_a()[g]; dvk_b = P.dvk_b()[g]; }
-    if (kLoadAhead) RVO3D_LOAD_INTEGRATION_STATE()
+    if (kLoadAhead) {  // the integration state (the same ten loads behind the barrier otherwise)
+      wpi = P.wp_idx()[g]; load3(P.prev(0), P.prev(1), P.prev(2), g, prev);
+      yaw = P.yaw()[g]; pitch = P.pitch()[g]; real_len = P.real_len()[g]; route_len = P.route_len()[g];
+      npts = P.n_points()[g]; f_arrive_in = P.arrive()[g] != 0; f_dest_in = P.dest()[g] != 0;
+    }
     bool have = false;
     if (P.dv_cached) have = dv_decode(dvk_a, dvk_b, dv);
     if (!have) {
-      if (!kLoadAhead) RVO3D_LOAD_PREV(P, g, prev);
+      if (!kLoadAhead) load3(P.prev(0), P.prev(1), P.prev(2), g, prev);
       const double p[3] = {S.x, S.y, S.z};
       des_vel(P, p, cur, dv);
       dev = deviation(prev, cur, p);
@@ -679,8 +674,11 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   RVO3D_STAMP(18);
   __syncthreads();  // everyone is done with the pre-move LDS image
   if (active) {
-    if (!kLoadAhead) RVO3D_LOAD_INTEGRATION_STATE()
-#undef RVO3D_LOAD_INTEGRATION_STATE
+    if (!kLoadAhead) {
+      wpi = P.wp_idx()[g]; load3(P.prev(0), P.prev(1), P.prev(2), g, prev);
+      yaw = P.yaw()[g]; pitch = P.pitch()[g]; real_len = P.real_len()[g]; route_len = P.route_len()[g];
+      npts = P.n_points()[g]; f_arrive_in = P.arrive()[g] != 0; f_dest_in = P.dest()[g] != 0;
+    }
     // extra_len is only ever WRITTEN by the step (drone.py:188, ir_gym.py:176): not loaded, and
     // stored only by the drones that set it; wp_idx / arrive / dest likewise only when they change
     bool ex_set = false;
@@ -719,8 +717,8 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
         wpi += 1;
         prev[0] = cur[0]; prev[1] = cur[1]; prev[2] = cur[2];
         load_wp(P, g, wpi, cur);
-        RVO3D_STORE_CUR(P, g, cur);
-        RVO3D_STORE_PREV(P, g, prev);
+        store3(P.cur(0), P.cur(1), P.cur(2), g, cur);
+        store3(P.prev(0), P.prev(1), P.prev(2), g, prev);
         f_arrive = false;
       }
     }
@@ -796,8 +794,7 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     double p[3] = {0, 0, 0}, rcur[3] = {0, 0, 0}, rdev = 0.0;
     uint32_t rdv_a = 0, rdv_b = 0;
     if (NW > 1 && active && P.prev_cnt) {  // (see phase 0; visible to early_zero_blocks behind the next barrier)
-      old_cnt = (uint32_t)P.prev_cnt[g];
-      old_cnt = old_cnt < (uint32_t)P.nm ? old_cnt : (uint32_t)P.nm;
+      old_cnt = old_kept(P, g);
       L.kept[lrow] = (int)old_cnt;
       if (old_cnt != 0) *L.any_old = 1;
     }
@@ -820,8 +817,8 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
         des_vel(P, p, cur, dv);
         dev = deviation(p, cur, p);  // previous_des = waypoints[0] = the start position
       }
-      RVO3D_STORE_CUR(P, g, cur);
-      RVO3D_STORE_PREV(P, g, p);
+      store3(P.cur(0), P.cur(1), P.cur(2), g, cur);
+      store3(P.prev(0), P.prev(1), P.prev(2), g, p);
       max_dev = dev > 0.0 ? dev : 0.0;
       P.wp_idx()[g] = 1; P.arrive()[g] = 0; P.dest()[g] = 0;
       P.real_len()[g] = 0.0; P.yaw()[g] = 0.0; P.pitch()[g] = 0.0;
