@@ -214,11 +214,12 @@ int launch_policy_mlp(const rvo3d::PolicyMlpArgs& A, unsigned grid, hipStream_t 
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
 }
-template <int H, int ND>
+template <int H, int ND, bool X3>
 int launch_policy_rnn_tiles(const rvo3d::RnnTilesArgs& A, unsigned grid, hipStream_t s) {
-  constexpr int lds = rvo3d::kRnnTilesWaves * H * 128;  // the running hidden state, 128 H bytes per wave
-  if (int rc = allow_dynamic_lds<rvo3d::policy_rnn_tiles_kernel<H, ND>>(lds)) return rc;
-  hipLaunchKernelGGL((rvo3d::policy_rnn_tiles_kernel<H, ND>), dim3(grid), dim3(64 * rvo3d::kRnnTilesWaves), lds, s, A);
+  // the running hidden state, 128 H bytes per wave (X3: afterwards the features' split fragments, the same size)
+  constexpr int lds = rvo3d::kRnnTilesWaves * H * 128;
+  if (int rc = allow_dynamic_lds<rvo3d::policy_rnn_tiles_kernel<H, ND, X3>>(lds)) return rc;
+  hipLaunchKernelGGL((rvo3d::policy_rnn_tiles_kernel<H, ND, X3>), dim3(grid), dim3(64 * rvo3d::kRnnTilesWaves), lds, s, A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
 }
@@ -345,6 +346,68 @@ std::array<ScalarField, 8> scalar_fields(const Params& P, const double* yaw, con
   return {{{yaw, P.yaw(), EN * 8}, {pitch, P.pitch(), EN * 8}, {real_len, P.real_len(), EN * 8},
            {max_dev, P.max_dev(), EN * 8}, {extra_len, P.extra_len(), EN * 8}, {wp_idx, P.wp_idx(), EN * 4},
            {arrive, P.arrive(), EN}, {dest, P.dest(), EN}}};
+}
+// rvo3d_policy_rnn_tiles* (X3 = false) and rvo3d_policy_rnn_tiles_x3* (X3 = true): the same arguments, checks (all of
+// them before the first HIP call), error texts and launch geometry; the precision picks the instantiations and the blob
+// layout.  (Called between the entry points' RVO3D_API_BEGIN / END.)
+template <bool X3>
+int64_t policy_rnn_tiles_blob_bytes(int32_t hidden, int32_t in_dim, int32_t state_dim, int32_t bidir) {
+  if (!rnn_tiles_shape_ok(hidden, in_dim, state_dim)) return -1;
+  return rvo3d::rnn_tiles_layout(hidden, bidir ? 2 : 1, X3).total;
+}
+
+template <bool X3>
+int policy_rnn_tiles_pack(const rvo3d_rnn_policy* net, void* blob, int64_t blob_bytes, void* stream) {
+  if (!net || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
+  rvo3d::RnnTilesPackArgs A;
+  if (int rc = copy_reader(A, *net)) return rc;
+  const bool bi = net->w_ih_r != nullptr;
+  if (!rnn_tiles_shape_ok(net->hidden, net->in_dim, net->state_dim))
+    return fail(RVO3D_ERR_INVALID, "rnn tiles: hidden must be 64 or 256, in_dim 9, state_dim 1..16");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  if (blob_bytes != policy_rnn_tiles_blob_bytes<X3>(net->hidden, net->in_dim, net->state_dim, bi))
+    return fail(RVO3D_ERR_INVALID, "blob_bytes does not match rvo3d_policy_rnn_tiles_blob_bytes for this shape");
+  if (int rc = copy_heads(A, net->pi, net->v, "null head weight")) return rc;
+  A.H = net->hidden; A.ND = bi ? 2 : 1; A.SD = net->state_dim; A.IN = net->in_dim;
+  A.blob = static_cast<unsigned char*>(blob);
+  hipLaunchKernelGGL(rvo3d::rnn_tiles_pack_kernel<X3>, dim3(128), dim3(256), 0, static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+}
+
+template <bool X3>
+int policy_rnn_tiles(const void* blob, int64_t blob_bytes, int32_t hidden, int32_t in_dim, int32_t state_dim,
+                     int32_t bidir, const float* obs, int64_t obs_ld, const int32_t* vo_count, const int32_t* list,
+                     int32_t* count, int32_t* done_blocks, int32_t* work, int64_t max_rows, int32_t slots,
+                     int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed, uint64_t step,
+                     float* act, float* logp, float* val, float* dbg_mu, void* stream) {
+  if (!blob || !obs || !vo_count || !list || !count || !done_blocks || !work || !log_std || !act || !logp || !val)
+    return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (!rnn_tiles_shape_ok(hidden, in_dim, state_dim))
+    return fail(RVO3D_ERR_INVALID, "rnn tiles: hidden must be 64 or 256, in_dim 9, state_dim 1..16");
+  if (slots < 1 || slots > rvo3d::kRnnTilesMaxSlots) return fail(RVO3D_ERR_INVALID, "slots must be 1..12");
+  // (the two precisions' blobs differ in size for every shape: a blob of the other one is refused here)
+  if (blob_bytes != policy_rnn_tiles_blob_bytes<X3>(hidden, in_dim, state_dim, bidir))
+    return fail(RVO3D_ERR_INVALID, "blob_bytes does not match this shape: the blob was packed for another one");
+  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
+  if (max_rows < 1 || max_rows > 0x7fffffff) return fail(RVO3D_ERR_INVALID, "max_rows must be 1..2^31-1");
+  if (obs_ld < state_dim + slots * in_dim) return fail(RVO3D_ERR_INVALID, "obs_ld < state_dim + slots * in_dim");
+  int dev = 0, cus = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  rvo3d::RnnTilesArgs A;
+  A.blob = static_cast<const unsigned char*>(blob);
+  A.obs = obs; A.obs_ld = obs_ld; A.cnt = vo_count; A.list = list; A.count = count; A.done_blocks = done_blocks;
+  A.work = work; A.max_rows = max_rows; A.SD = state_dim; A.slots = slots;
+  A.S = sample_args(tanh_out, log_std, std_factor, seed, step, 0, act, logp, val, dbg_mu, nullptr);
+  A.S.step_dev = nullptr;  // (never graph-replayed: the noise counter is `step` alone)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rvo3d::rnn_tiles_bucket_kernel, dim3(256), dim3(256), 0, s, A);
+  HIP_TRY(hipGetLastError());
+  const unsigned grid = (unsigned)(cus > 0 ? cus : 1);  // one workgroup (four independent waves) per CU, persistent
+  if (hidden == 64)
+    return bidir ? launch_policy_rnn_tiles<64, 2, X3>(A, grid, s) : launch_policy_rnn_tiles<64, 1, X3>(A, grid, s);
+  return bidir ? launch_policy_rnn_tiles<256, 2, X3>(A, grid, s) : launch_policy_rnn_tiles<256, 1, X3>(A, grid, s);
 }
 }  // namespace
 
@@ -736,8 +799,7 @@ int rvo3d_policy_rows(const rvo3d_rnn_policy* net, const float* obs, int64_t obs
 // The biGRU policy step of the listed rows in 32-row MFMA tiles (csrc/rvo3d_policy_rnn_tiles.hpp): a bucket launch sorts
 // the list into per-count sub-lists, a persistent launch runs the tiles.
 int64_t rvo3d_policy_rnn_tiles_blob_bytes(int32_t hidden, int32_t in_dim, int32_t state_dim, int32_t bidir) {
-  if (!rnn_tiles_shape_ok(hidden, in_dim, state_dim)) return -1;
-  return rvo3d::rnn_tiles_layout(hidden, bidir ? 2 : 1).total;
+  return policy_rnn_tiles_blob_bytes<false>(hidden, in_dim, state_dim, bidir);
 }
 
 int64_t rvo3d_policy_rnn_tiles_work_bytes(int64_t max_rows, int32_t slots) {
@@ -747,21 +809,7 @@ int64_t rvo3d_policy_rnn_tiles_work_bytes(int64_t max_rows, int32_t slots) {
 
 int rvo3d_policy_rnn_tiles_pack(const rvo3d_rnn_policy* net, void* blob, int64_t blob_bytes, void* stream) {
   RVO3D_API_BEGIN
-  if (!net || !blob) return fail(RVO3D_ERR_INVALID, "null pointer");
-  rvo3d::RnnTilesPackArgs A;
-  if (int rc = copy_reader(A, *net)) return rc;
-  const bool bi = net->w_ih_r != nullptr;
-  if (!rnn_tiles_shape_ok(net->hidden, net->in_dim, net->state_dim))
-    return fail(RVO3D_ERR_INVALID, "rnn tiles: hidden must be 64 or 256, in_dim 9, state_dim 1..16");
-  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
-  if (blob_bytes != rvo3d_policy_rnn_tiles_blob_bytes(net->hidden, net->in_dim, net->state_dim, bi))
-    return fail(RVO3D_ERR_INVALID, "blob_bytes does not match rvo3d_policy_rnn_tiles_blob_bytes for this shape");
-  if (int rc = copy_heads(A, net->pi, net->v, "null head weight")) return rc;
-  A.H = net->hidden; A.ND = bi ? 2 : 1; A.SD = net->state_dim; A.IN = net->in_dim;
-  A.blob = static_cast<unsigned char*>(blob);
-  hipLaunchKernelGGL(rvo3d::rnn_tiles_pack_kernel, dim3(128), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-  HIP_TRY(hipGetLastError());
-  return RVO3D_OK;
+  return policy_rnn_tiles_pack<false>(net, blob, blob_bytes, stream);
   RVO3D_API_END
 }
 
@@ -771,31 +819,34 @@ int rvo3d_policy_rnn_tiles(const void* blob, int64_t blob_bytes, int32_t hidden,
                            int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed, uint64_t step,
                            float* act, float* logp, float* val, float* dbg_mu, void* stream) {
   RVO3D_API_BEGIN
-  if (!blob || !obs || !vo_count || !list || !count || !done_blocks || !work || !log_std || !act || !logp || !val)
-    return fail(RVO3D_ERR_INVALID, "null pointer");
-  if (!rnn_tiles_shape_ok(hidden, in_dim, state_dim))
-    return fail(RVO3D_ERR_INVALID, "rnn tiles: hidden must be 64 or 256, in_dim 9, state_dim 1..16");
-  if (slots < 1 || slots > rvo3d::kRnnTilesMaxSlots) return fail(RVO3D_ERR_INVALID, "slots must be 1..12");
-  if (blob_bytes != rvo3d_policy_rnn_tiles_blob_bytes(hidden, in_dim, state_dim, bidir))
-    return fail(RVO3D_ERR_INVALID, "blob_bytes does not match this shape: the blob was packed for another one");
-  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(RVO3D_ERR_INVALID, "blob must be 16-byte aligned");
-  if (max_rows < 1 || max_rows > 0x7fffffff) return fail(RVO3D_ERR_INVALID, "max_rows must be 1..2^31-1");
-  if (obs_ld < state_dim + slots * in_dim) return fail(RVO3D_ERR_INVALID, "obs_ld < state_dim + slots * in_dim");
-  int dev = 0, cus = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  rvo3d::RnnTilesArgs A;
-  A.blob = static_cast<const unsigned char*>(blob);
-  A.obs = obs; A.obs_ld = obs_ld; A.cnt = vo_count; A.list = list; A.count = count; A.done_blocks = done_blocks;
-  A.work = work; A.max_rows = max_rows; A.SD = state_dim; A.slots = slots;
-  A.S = sample_args(tanh_out, log_std, std_factor, seed, step, 0, act, logp, val, dbg_mu, nullptr);
-  A.S.step_dev = nullptr;  // (never graph-replayed: the noise counter is `step` alone)
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rvo3d::rnn_tiles_bucket_kernel, dim3(256), dim3(256), 0, s, A);
-  HIP_TRY(hipGetLastError());
-  const unsigned grid = (unsigned)(cus > 0 ? cus : 1);  // one workgroup (four independent waves) per CU, persistent
-  if (hidden == 64) return bidir ? launch_policy_rnn_tiles<64, 2>(A, grid, s) : launch_policy_rnn_tiles<64, 1>(A, grid, s);
-  return bidir ? launch_policy_rnn_tiles<256, 2>(A, grid, s) : launch_policy_rnn_tiles<256, 1>(A, grid, s);
+  return policy_rnn_tiles<false>(blob, blob_bytes, hidden, in_dim, state_dim, bidir, obs, obs_ld, vo_count, list, count,
+                                 done_blocks, work, max_rows, slots, tanh_out, log_std, std_factor, seed, step, act, logp,
+                                 val, dbg_mu, stream);
+  RVO3D_API_END
+}
+
+// The float32-class twin of the trio above: the stacks behind the LayerNorm in split bf16 as the GRU's products already
+// are (see csrc/rvo3d_policy_rnn_tiles.hpp), on a blob of its own layout and size; same work area, list, counters,
+// noise and per-row tail.
+int64_t rvo3d_policy_rnn_tiles_x3_blob_bytes(int32_t hidden, int32_t in_dim, int32_t state_dim, int32_t bidir) {
+  return policy_rnn_tiles_blob_bytes<true>(hidden, in_dim, state_dim, bidir);
+}
+
+int rvo3d_policy_rnn_tiles_x3_pack(const rvo3d_rnn_policy* net, void* blob, int64_t blob_bytes, void* stream) {
+  RVO3D_API_BEGIN
+  return policy_rnn_tiles_pack<true>(net, blob, blob_bytes, stream);
+  RVO3D_API_END
+}
+
+int rvo3d_policy_rnn_tiles_x3(const void* blob, int64_t blob_bytes, int32_t hidden, int32_t in_dim, int32_t state_dim,
+                              int32_t bidir, const float* obs, int64_t obs_ld, const int32_t* vo_count,
+                              const int32_t* list, int32_t* count, int32_t* done_blocks, int32_t* work, int64_t max_rows,
+                              int32_t slots, int32_t tanh_out, const float* log_std, float std_factor, uint64_t seed,
+                              uint64_t step, float* act, float* logp, float* val, float* dbg_mu, void* stream) {
+  RVO3D_API_BEGIN
+  return policy_rnn_tiles<true>(blob, blob_bytes, hidden, in_dim, state_dim, bidir, obs, obs_ld, vo_count, list, count,
+                                done_blocks, work, max_rows, slots, tanh_out, log_std, std_factor, seed, step, act, logp,
+                                val, dbg_mu, stream);
   RVO3D_API_END
 }
 

@@ -30,6 +30,11 @@
 // of their own (with plain bf16 operands a 12-step row's mu was 2.5x further from the float32 module than the library
 // GEMM path's).  The first step needs no recurrent product (h = 0).  The stacks behind the LayerNorm are bf16 operands
 // with float32 accumulation, as the "heads" path's GEMMs; gate math, LayerNorm and the hidden state are float32.
+// The X3 instantiations (rvo3d_policy_rnn_tiles_x3, float32 rollouts and evaluations) split the stacks as well: the
+// LayerNorm output and the ReLU'd float32 sums of both hidden layers become hi and lo B fragments, W1 / W2 / W3 are packed
+// as hi and lo blocks and go through mfma_x3_part - float32-class from end to end (mu and v within 1e-4 of a float64
+// forward, where the bf16 stacks are 1e-3 off).  Their blob has its own magic word and size; a kernel given the other
+// precision's blob computes nothing.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,14 +52,16 @@ constexpr int kRnnTilesMaxSlots = 12;
 constexpr int kRnnTilesWaves = 4;         // waves per workgroup (independent: one tile each)
 constexpr int kRnnTilesWorkHeader = 32;   // int32 cursors (count 1..slots) before the sub-lists
 constexpr int32_t kRnnTilesMagic = 0x524e5431;
+constexpr int32_t kRnnTilesMagicX3 = 0x524e5833;  // the float32-class blob (X3 = true below): its own word, its own size
 constexpr int kRnnTilesHeadBytes = 64;
 
 // byte offsets inside the blob (every section 16-byte aligned; one fragment = 64 lanes x 8 bf16 = 1 KB)
 struct RnnTilesLayout {
   int64_t wih[2], whh[2], bih[2], bhn[2], ln_hg, ln_hb, ln_pg, ln_pb, w1[2], b1[2], w2[2], b2[2], w3[2], hb[2], total;
 };
-__host__ __device__ inline RnnTilesLayout rnn_tiles_layout(int H, int ND) {
-  const int HT = H / 32, KH = H / 16, KS1 = KH + 1;
+// X3: the stacks' weights as split fragments too (a hi 1 KB block followed by its lo block, as wih / whh)
+__host__ __device__ inline RnnTilesLayout rnn_tiles_layout(int H, int ND, bool X3 = false) {
+  const int HT = H / 32, KH = H / 16, KS1 = KH + 1, FB = X3 ? 2048 : 1024;
   RnnTilesLayout L{};
   int64_t o = kRnnTilesHeadBytes;
   for (int d = 0; d < 2; ++d) {
@@ -69,11 +76,11 @@ __host__ __device__ inline RnnTilesLayout rnn_tiles_layout(int H, int ND) {
   L.ln_pg = o; o += 64;                                            // [16] float
   L.ln_pb = o; o += 64;
   for (int n = 0; n < 2; ++n) {
-    L.w1[n] = o; o += (int64_t)8 * KS1 * 1024;                     // [tile][k-step][lane][8]; k-step KH = the state
+    L.w1[n] = o; o += (int64_t)8 * KS1 * FB;                       // [tile][k-step][lane][8]; k-step KH = the state
     L.b1[n] = o; o += 8 * 128;                                     // [tile][h][16] float
-    L.w2[n] = o; o += (int64_t)8 * 16 * 1024;
+    L.w2[n] = o; o += (int64_t)8 * 16 * FB;
     L.b2[n] = o; o += 8 * 128;
-    L.w3[n] = o; o += 16 * 1024;                                   // [k-step][lane][8]: rows 0..2 (actor) / 0 (critic)
+    L.w3[n] = o; o += 16 * FB;                                     // [k-step][lane][8]: rows 0..2 (actor) / 0 (critic)
     L.hb[n] = o; o += 16;                                          // float[4]
   }
   L.total = o;
@@ -89,11 +96,11 @@ struct RnnTilesPackArgs {
   const float *w1[2], *b1[2], *w2[2], *b2[2], *w3[2], *b3[2];
   unsigned char* blob;
 };
+template <bool X3>
 __global__ void __launch_bounds__(256) rnn_tiles_pack_kernel(const RnnTilesPackArgs A) {
   const int H = A.H, HT = H / 32, KH = H / 16, KS1 = KH + 1, SD = A.SD, IN = A.IN, D = SD + H;
-  const RnnTilesLayout L = rnn_tiles_layout(H, A.ND);
+  const RnnTilesLayout L = rnn_tiles_layout(H, A.ND, X3);
   unsigned char* const b = A.blob;
-  auto bf = [&](int64_t off, int64_t i, float v) { reinterpret_cast<uint16_t*>(b + off)[i] = f32_to_bf16_rne(v); };
   auto fl = [&](int64_t off, int64_t i, float v) { reinterpret_cast<float*>(b + off)[i] = v; };
   // a split fragment: element i of the logical [..][lane][8] array at 1 KB blocks 2 f (hi = bf16(v)) and 2 f + 1 (lo)
   auto split = [&](int64_t off, int64_t i, float v) {
@@ -103,9 +110,14 @@ __global__ void __launch_bounds__(256) rnn_tiles_pack_kernel(const RnnTilesPackA
     reinterpret_cast<uint16_t*>(b + off)[at] = hi;
     reinterpret_cast<uint16_t*>(b + off)[at + 512] = lo;
   };
+  // a fragment of the stacks: one bf16 block, or - X3 - split like the GRU's
+  auto bf = [&](int64_t off, int64_t i, float v) {
+    if constexpr (X3) split(off, i, v);
+    else reinterpret_cast<uint16_t*>(b + off)[i] = f32_to_bf16_rne(v);
+  };
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t0 < 16) reinterpret_cast<int32_t*>(b)[t0] = t0 == 0 ? kRnnTilesMagic : t0 == 1 ? H : t0 == 2 ? SD : t0 == 3 ? A.ND : t0 == 4 ? IN : t0 == 5 ? __builtin_bit_cast(int32_t, A.eps) : 0;
+  if (t0 < 16) reinterpret_cast<int32_t*>(b)[t0] = t0 == 0 ? (X3 ? kRnnTilesMagicX3 : kRnnTilesMagic) : t0 == 1 ? H : t0 == 2 ? SD : t0 == 3 ? A.ND : t0 == 4 ? IN : t0 == 5 ? __builtin_bit_cast(int32_t, A.eps) : 0;
   for (int d = 0; d < A.ND; ++d) {
     for (int64_t i = t0; i < (int64_t)3 * HT * 512; i += stride) {  // W_ih, columns IN..15 zero
       const int j = i & 7, lane = (i >> 3) & 63, gm = (int)(i >> 9), g = gm / HT, m = gm % HT;
@@ -229,7 +241,8 @@ constexpr int kRnnTilesDepth = 16;  // fragments in flight per wave
 
 // ---- the policy step of the listed rows ------------------------------------------------------------------------------
 // H: reader hidden width (64 or 256), ND: directions (1 GRU, 2 biGRU).  One wave = one 32-row tile at a time.
-template <int H, int ND>
+// X3: the stacks behind the LayerNorm in split bf16 as well (float32-class from end to end), on a blob packed for it.
+template <int H, int ND, bool X3 = false>
 __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(const RnnTilesArgs A) {
   constexpr int HT = H / 32, KH = H / 16, KS1 = KH + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -238,10 +251,10 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
   // the running direction's hidden state, float32, in LDS (VGPRs are short: fragments, accumulators and the state's
   // bf16 operand copy live there): [tile][register / 4][lane] float4, lane-linear
   float4* const hst = reinterpret_cast<float4*>(smem) + wave * HT * 4 * 64;
-  const RnnTilesLayout L = rnn_tiles_layout(H, ND);
+  const RnnTilesLayout L = rnn_tiles_layout(H, ND, X3);
   const unsigned char* const blob0 = A.blob;
   const int32_t* const hdr = reinterpret_cast<const int32_t*>(blob0);
-  const bool shape_ok = hdr[0] == kRnnTilesMagic && hdr[1] == H && hdr[2] == A.SD && hdr[3] == ND;
+  const bool shape_ok = hdr[0] == (X3 ? kRnnTilesMagicX3 : kRnnTilesMagic) && hdr[1] == H && hdr[2] == A.SD && hdr[3] == ND;
   const SampleConsts SC = sample_consts(A.S);
   // tiles per count, longest counts first
   int ntile[kRnnTilesMaxSlots], total = 0;
@@ -412,80 +425,195 @@ __global__ void __launch_bounds__(64 * kRnnTilesWaves) policy_rnn_tiles_kernel(c
 #pragma unroll
     for (int k = 0; k < 16; ++k) if (k < A.SD) { const float dv = p[k] - mean; s2 += dv * dv; }
     const float rstd = 1.0f / __builtin_sqrtf(s2 / Df + __builtin_bit_cast(float, hdr[5]));
-    u32x4 F[KS1];  // the features as the B fragments of the first layers
+    if constexpr (X3) {
+      // ---- float32-class stacks: every operand hi / lo, every product mfma_x3_part, one fixed summation order ----
+      // The features' hidden k-steps go to LDS as split B fragments, [k-step][hi, lo][lane]: the state area is dead
+      // once the recurrence is over and exactly that large, and a lane reads back only what it wrote itself (no
+      // barrier).  Both stacks re-read them; the state k-step stays in registers.
+      u32x4* const fl = reinterpret_cast<u32x4*>(hst);
 #pragma unroll
-    for (int m = 0; m < HT; ++m) {
-      const f32x16 g = load_ctab_global(blob + L.ln_hg, m, h), bb = load_ctab_global(blob + L.ln_hb, m, h);
+      for (int m = 0; m < HT; ++m) {
+        const f32x16 g = load_ctab_global(blob + L.ln_hg, m, h), bb = load_ctab_global(blob + L.ln_hb, m, h);
+        u32x4 fh[2], fo[2];
 #pragma unroll
-      for (int q = 0; q < 8; ++q)
-        F[2 * m + (q >> 2)][q & 3] = pack_bf16x2((hs[m][2 * q] - mean) * rstd * g[2 * q] + bb[2 * q],
-                                                 (hs[m][2 * q + 1] - mean) * rstd * g[2 * q + 1] + bb[2 * q + 1]);
-    }
-    {
-      float pg[16], pb[16];
+        for (int q = 0; q < 8; ++q) {
+          const Bf16x2Split sp = split_bf16x2((hs[m][2 * q] - mean) * rstd * g[2 * q] + bb[2 * q],
+                                              (hs[m][2 * q + 1] - mean) * rstd * g[2 * q + 1] + bb[2 * q + 1]);
+          fh[q >> 2][q & 3] = sp.hi;
+          fo[q >> 2][q & 3] = sp.lo;
+        }
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const f32x4 g4 = ld_blob<f32x4>(blob + L.ln_pg + 16 * k), b4 = ld_blob<f32x4>(blob + L.ln_pb + 16 * k);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { pg[4 * k + u] = g4[u]; pb[4 * k + u] = b4[u]; }
+        for (int t = 0; t < 2; ++t) {
+          fl[(2 * (2 * m + t)) * 64 + lane] = fh[t];
+          fl[(2 * (2 * m + t) + 1) * 64 + lane] = fo[t];
+        }
       }
-      f32x8 fv;
+      u32x4 fsh, fsl;  // the state k-step
+      {
+        float pg[16], pb[16];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float pk = h ? p[8 + q] : p[q];
-        fv[q] = 8 * h + q < A.SD ? (pk - mean) * rstd * pg[8 * h + q] + pb[8 * h + q] : 0.f;
+        for (int k = 0; k < 4; ++k) {
+          const f32x4 g4 = ld_blob<f32x4>(blob + L.ln_pg + 16 * k), b4 = ld_blob<f32x4>(blob + L.ln_pb + 16 * k);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) { pg[4 * k + u] = g4[u]; pb[4 * k + u] = b4[u]; }
+        }
+        f32x8 fv;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const float pk = h ? p[8 + q] : p[q];
+          fv[q] = 8 * h + q < A.SD ? (pk - mean) * rstd * pg[8 * h + q] + pb[8 * h + q] : 0.f;
+        }
+        bf16x8 sh, sl;
+        split8(fv, sh, sl);
+        fsh = __builtin_bit_cast(u32x4, sh);
+        fsl = __builtin_bit_cast(u32x4, sl);
       }
-      F[KH] = __builtin_bit_cast(u32x4, __builtin_convertvector(fv, bf16x8));
-    }
-
-    // ---- the two stacks: relu(W1 f + b1) -> relu(W2 . + b2) -> W3 . + b3 ----
 #pragma unroll 1
-    for (int net = 0; net < 2; ++net) {
-      const unsigned char* blob = blob0;
-      asm volatile("" : "+s"(blob));  // (as in the recurrence)
-      const unsigned char* const base = blob + lane * 16;
-      const int64_t o1 = L.w1[net], o2 = L.w2[net], o3 = L.w3[net];
-      u32x4 H1[16];
-      f32x16 acc;
-      frag_stream<kRnnTilesDepth, 8 * KS1>(
-          base, [&](int i) RVO3D_INLINE -> int64_t { return o1 + (int64_t)i * 1024; },
-          [&](auto ic, const bf16x8& a) RVO3D_INLINE {
-            constexpr int i = decltype(ic)::value, m = i / KS1, s1 = i % KS1;
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, F[s1]),
-                                                          s1 == 0 ? load_ctab_global(blob + L.b1[net], m, h) : acc, 0, 0, 0);
-            if constexpr (s1 == KS1 - 1) {
+      for (int net = 0; net < 2; ++net) {
+        const unsigned char* blob = blob0;
+        asm volatile("" : "+s"(blob));  // (as in the recurrence)
+        const unsigned char* const base = blob + lane * 16;
+        // (every offset of this net read once, here: L is indexed by a runtime net, i.e. it lives in scratch, and a
+        // bias table fetched by L.b1[net] inside a stream is a scratch read between its MFMAs)
+        const int64_t o1 = L.w1[net], o2 = L.w2[net], o3 = L.w3[net], ob1 = L.b1[net], ob2 = L.b2[net], ohb = L.hb[net];
+        // The second layer is summed over k as the first layer produces it: unit tile m of H1 (two k-steps, split after
+        // the ReLU) goes straight into all eight output tiles of the second layer, whose accumulators are kept - so H1
+        // is never held whole (hi and lo of 16 k-steps would be 128 registers next to the fragment ring).  Per output
+        // element the k-steps still come in ascending order, hi-hi, hi-lo, lo-hi each.
+        constexpr int PER1 = 2 * KS1, PER = PER1 + 32;  // fragments per unit tile: W1's, then W2's (tile, k-step, hi / lo)
+        f32x16 acc, acc2[8];
+        u32x4 bh, bl, h1h[2], h1l[2];
+        frag_stream<kRnnTilesDepth, 8 * PER>(
+            base,
+            [&](int i) RVO3D_INLINE -> int64_t {
+              const int m = i / PER, q = i % PER;
+              if (q < PER1) return o1 + (int64_t)(m * PER1 + q) * 1024;
+              const int j = q - PER1, m2 = j >> 2, t = (j >> 1) & 1;
+              return o2 + (int64_t)((m2 * 16 + 2 * m + t) * 2 + (j & 1)) * 1024;
+            },
+            [&](auto ic, const bf16x8& a) RVO3D_INLINE {
+              constexpr int i = decltype(ic)::value, m = i / PER, q = i % PER;
+              if constexpr (q < PER1) {
+                constexpr int s1 = q >> 1, part = q & 1;
+                if constexpr (q == 0) acc = load_ctab_global(blob + ob1, m, h);
+                if constexpr (part == 0) {
+                  if constexpr (s1 < KH) { bh = fl[(2 * s1) * 64 + lane]; bl = fl[(2 * s1 + 1) * 64 + lane]; }
+                  else { bh = fsh; bl = fsl; }
+                }
+                mfma_x3_part(acc, a, part, __builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, bl));
+                if constexpr (q == PER1 - 1) {
 #pragma unroll
-              for (int q = 0; q < 8; ++q) H1[2 * m + (q >> 2)][q & 3] = pack_bf16x2(relu_f32(acc[2 * q]), relu_f32(acc[2 * q + 1]));
-            }
-          });
-      // second layer (16 k-steps per tile) with the head's two k-steps of the tile behind it: 18 fragments per tile
-      f32x16 hd = {0};
-      u32x4 h2[2];
-      frag_stream<kRnnTilesDepth, 8 * 18>(
-          base,
-          [&](int i) RVO3D_INLINE -> int64_t {
-            const int m = i / 18, q = i % 18;
-            return q < 16 ? o2 + (int64_t)(m * 16 + q) * 1024 : o3 + (int64_t)(2 * m + q - 16) * 1024;
-          },
-          [&](auto ic, const bf16x8& a) RVO3D_INLINE {
-            constexpr int i = decltype(ic)::value, m = i / 18, q = i % 18;
-            if constexpr (q < 16) {
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, H1[q]),
-                                                            q == 0 ? load_ctab_global(blob + L.b2[net], m, h) : acc, 0, 0, 0);
-              if constexpr (q == 15) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) h2[k >> 2][k & 3] = pack_bf16x2(relu_f32(acc[2 * k]), relu_f32(acc[2 * k + 1]));
+                  for (int k = 0; k < 8; ++k) {
+                    const Bf16x2Split sp = split_bf16x2(relu_f32(acc[2 * k]), relu_f32(acc[2 * k + 1]));
+                    h1h[k >> 2][k & 3] = sp.hi;
+                    h1l[k >> 2][k & 3] = sp.lo;
+                  }
+                }
+              } else {
+                constexpr int j = q - PER1, m2 = j >> 2, t = (j >> 1) & 1, part = j & 1;
+                if constexpr (m == 0 && t == 0 && part == 0) acc2[m2] = load_ctab_global(blob + ob2, m2, h);
+                mfma_x3_part(acc2[m2], a, part, __builtin_bit_cast(bf16x8, h1h[t]), __builtin_bit_cast(bf16x8, h1l[t]));
               }
-            } else {
-              hd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, h2[q - 16]), hd, 0, 0, 0);
-            }
-          });
-      // head rows 0..2 sit in registers 0..2 of lanes 0..31
-      const f32x4 hb4 = ld_blob<f32x4>(blob + L.hb[net]);
-      const float4 hb = {hb4[0], hb4[1], hb4[2], hb4[3]};
-      if (h == 0 && valid) {
-        if (net == 0) finish_row(A.S, SC, row, hd[0] + hb.x, hd[1] + hb.y, hd[2] + hb.z);
-        else A.S.val[row] = hd[0] + hb.x;
+            });
+        // the head: output tile m2 of the second layer, ReLU, split, its two k-steps
+        f32x16 hd = {0};
+        u32x4 h2h[2], h2l[2];
+        frag_stream<kRnnTilesDepth, 32>(
+            base, [&](int i) RVO3D_INLINE -> int64_t { return o3 + (int64_t)i * 1024; },
+            [&](auto ic, const bf16x8& a) RVO3D_INLINE {
+              constexpr int i = decltype(ic)::value, m2 = i >> 2, t = (i >> 1) & 1, part = i & 1;
+              if constexpr ((i & 3) == 0) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                  const Bf16x2Split sp = split_bf16x2(relu_f32(acc2[m2][2 * k]), relu_f32(acc2[m2][2 * k + 1]));
+                  h2h[k >> 2][k & 3] = sp.hi;
+                  h2l[k >> 2][k & 3] = sp.lo;
+                }
+              }
+              mfma_x3_part(hd, a, part, __builtin_bit_cast(bf16x8, h2h[t]), __builtin_bit_cast(bf16x8, h2l[t]));
+            });
+        const f32x4 hb4 = ld_blob<f32x4>(blob + ohb);
+        if (h == 0 && valid) {
+          if (net == 0) finish_row(A.S, SC, row, hd[0] + hb4[0], hd[1] + hb4[1], hd[2] + hb4[2]);
+          else A.S.val[row] = hd[0] + hb4[0];
+        }
+      }
+    } else {
+      u32x4 F[KS1];  // the features as the B fragments of the first layers
+  #pragma unroll
+      for (int m = 0; m < HT; ++m) {
+        const f32x16 g = load_ctab_global(blob + L.ln_hg, m, h), bb = load_ctab_global(blob + L.ln_hb, m, h);
+  #pragma unroll
+        for (int q = 0; q < 8; ++q)
+          F[2 * m + (q >> 2)][q & 3] = pack_bf16x2((hs[m][2 * q] - mean) * rstd * g[2 * q] + bb[2 * q],
+                                                   (hs[m][2 * q + 1] - mean) * rstd * g[2 * q + 1] + bb[2 * q + 1]);
+      }
+      {
+        float pg[16], pb[16];
+  #pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const f32x4 g4 = ld_blob<f32x4>(blob + L.ln_pg + 16 * k), b4 = ld_blob<f32x4>(blob + L.ln_pb + 16 * k);
+  #pragma unroll
+          for (int u = 0; u < 4; ++u) { pg[4 * k + u] = g4[u]; pb[4 * k + u] = b4[u]; }
+        }
+        f32x8 fv;
+  #pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const float pk = h ? p[8 + q] : p[q];
+          fv[q] = 8 * h + q < A.SD ? (pk - mean) * rstd * pg[8 * h + q] + pb[8 * h + q] : 0.f;
+        }
+        F[KH] = __builtin_bit_cast(u32x4, __builtin_convertvector(fv, bf16x8));
+      }
+
+      // ---- the two stacks: relu(W1 f + b1) -> relu(W2 . + b2) -> W3 . + b3 ----
+  #pragma unroll 1
+      for (int net = 0; net < 2; ++net) {
+        const unsigned char* blob = blob0;
+        asm volatile("" : "+s"(blob));  // (as in the recurrence)
+        const unsigned char* const base = blob + lane * 16;
+        const int64_t o1 = L.w1[net], o2 = L.w2[net], o3 = L.w3[net];
+        u32x4 H1[16];
+        f32x16 acc;
+        frag_stream<kRnnTilesDepth, 8 * KS1>(
+            base, [&](int i) RVO3D_INLINE -> int64_t { return o1 + (int64_t)i * 1024; },
+            [&](auto ic, const bf16x8& a) RVO3D_INLINE {
+              constexpr int i = decltype(ic)::value, m = i / KS1, s1 = i % KS1;
+              acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, F[s1]),
+                                                            s1 == 0 ? load_ctab_global(blob + L.b1[net], m, h) : acc, 0, 0, 0);
+              if constexpr (s1 == KS1 - 1) {
+  #pragma unroll
+                for (int q = 0; q < 8; ++q) H1[2 * m + (q >> 2)][q & 3] = pack_bf16x2(relu_f32(acc[2 * q]), relu_f32(acc[2 * q + 1]));
+              }
+            });
+        // second layer (16 k-steps per tile) with the head's two k-steps of the tile behind it: 18 fragments per tile
+        f32x16 hd = {0};
+        u32x4 h2[2];
+        frag_stream<kRnnTilesDepth, 8 * 18>(
+            base,
+            [&](int i) RVO3D_INLINE -> int64_t {
+              const int m = i / 18, q = i % 18;
+              return q < 16 ? o2 + (int64_t)(m * 16 + q) * 1024 : o3 + (int64_t)(2 * m + q - 16) * 1024;
+            },
+            [&](auto ic, const bf16x8& a) RVO3D_INLINE {
+              constexpr int i = decltype(ic)::value, m = i / 18, q = i % 18;
+              if constexpr (q < 16) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, H1[q]),
+                                                              q == 0 ? load_ctab_global(blob + L.b2[net], m, h) : acc, 0, 0, 0);
+                if constexpr (q == 15) {
+  #pragma unroll
+                  for (int k = 0; k < 8; ++k) h2[k >> 2][k & 3] = pack_bf16x2(relu_f32(acc[2 * k]), relu_f32(acc[2 * k + 1]));
+                }
+              } else {
+                hd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, h2[q - 16]), hd, 0, 0, 0);
+              }
+            });
+        // head rows 0..2 sit in registers 0..2 of lanes 0..31
+        const f32x4 hb4 = ld_blob<f32x4>(blob + L.hb[net]);
+        const float4 hb = {hb4[0], hb4[1], hb4[2], hb4[3]};
+        if (h == 0 && valid) {
+          if (net == 0) finish_row(A.S, SC, row, hd[0] + hb.x, hd[1] + hb.y, hd[2] + hb.z);
+          else A.S.val[row] = hd[0] + hb.x;
+        }
       }
     }
   }

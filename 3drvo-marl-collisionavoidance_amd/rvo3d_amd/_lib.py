@@ -119,7 +119,8 @@ SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_reset",
            "rvo3d_policy_mlp_sample", "rvo3d_policy_mlp_x3_blob_bytes", "rvo3d_policy_mlp_x3_pack", "rvo3d_policy_mlp_x3_sample",
            "rvo3d_reader_zero_features", "rvo3d_policy_rows",
            "rvo3d_policy_rnn_tiles_blob_bytes", "rvo3d_policy_rnn_tiles_pack", "rvo3d_policy_rnn_tiles_work_bytes",
-           "rvo3d_policy_rnn_tiles", "rvo3d_reader_first_step", "rvo3d_rollout_account", "rvo3d_rollout_set_step_counter", "rvo3d_gae",
+           "rvo3d_policy_rnn_tiles", "rvo3d_policy_rnn_tiles_x3_blob_bytes", "rvo3d_policy_rnn_tiles_x3_pack",
+           "rvo3d_policy_rnn_tiles_x3", "rvo3d_reader_first_step", "rvo3d_rollout_account", "rvo3d_rollout_set_step_counter", "rvo3d_gae",
            "rvo3d_eval_action", "rvo3d_eval_account", "rvo3d_observe_envs", "rvo3d_set_reward_f64",
            "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
@@ -127,7 +128,8 @@ SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_reset",
 # the symbols that return a byte count (int64, negative: shape not supported); every other one but
 # rvo3d_last_error returns an int32 (a status, or the version)
 INT64_SYMBOLS = ("rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_x3_blob_bytes",
-                 "rvo3d_policy_rnn_tiles_blob_bytes", "rvo3d_policy_rnn_tiles_work_bytes")
+                 "rvo3d_policy_rnn_tiles_blob_bytes", "rvo3d_policy_rnn_tiles_work_bytes",
+                 "rvo3d_policy_rnn_tiles_x3_blob_bytes")
 
 _lib = None
 
@@ -171,6 +173,9 @@ def lib():
     L.rvo3d_policy_rnn_tiles_work_bytes.argtypes = [C.c_int64, i32]
     L.rvo3d_policy_rnn_tiles.argtypes = [vp, C.c_int64, i32, i32, i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64,
                                          i32, i32, vp, C.c_float, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
+    L.rvo3d_policy_rnn_tiles_x3_blob_bytes.argtypes = L.rvo3d_policy_rnn_tiles_blob_bytes.argtypes
+    L.rvo3d_policy_rnn_tiles_x3_pack.argtypes = L.rvo3d_policy_rnn_tiles_pack.argtypes
+    L.rvo3d_policy_rnn_tiles_x3.argtypes = L.rvo3d_policy_rnn_tiles.argtypes
     L.rvo3d_reader_first_step.argtypes = [C.POINTER(GruReader), vp, C.c_int64, C.c_int64, vp, i32, C.c_int64, vp]
     L.rvo3d_rollout_set_step_counter.argtypes = [vp]
     L.rvo3d_rollout_account.argtypes = [i32, i32, vp, vp, vp, i32, i32, i32] + [vp] * 8

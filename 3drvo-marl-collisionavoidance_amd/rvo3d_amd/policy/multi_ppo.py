@@ -191,7 +191,7 @@ class multi_ppo:
                  max_update_num=None, mpi=False, figure_save_path=None, minibatch_size=None,
                  dist=None, sanitize_rewards=True, amp=False, reference_order=False, fused_rollout=True,
                  tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False,
-                 fused_rnn_tiles=False, fused_gae=False, **kwargs):
+                 fused_rnn_tiles=False, fused_gae=False, fused_rnn_fp32=False, **kwargs):
         np.random.seed(seed)
         self.env, self.ac, self.dist = env, ac_policy, dist
         # The agent order of the reference-order update comes from a generator of its own, seeded like
@@ -221,6 +221,18 @@ class multi_ppo:
                 raise ValueError("fused_rnn_tiles=True needs an rnn_ac with a shared GRU / biGRU reader of hidden 64 or "
                                  "256, in_dim 9, state_dim <= 16, (256, 256) ReLU heads, on a GPU, and 1..12 VO slots")
         self.fused_rnn_tiles = bool(fused_rnn_tiles)
+        # float32 rollouts (amp=False) of the same actor-critic: mode "rnn_tiles_x3" - the "rnn_tiles" launches on the
+        # float32-class kernels (the collapsed zero-VO layer through rvo3d_policy_mlp_x3_sample, the rows with VO rows
+        # through rvo3d_policy_rnn_tiles_x3) instead of the "heads" mode's float32 library GEMMs; opt-in, eager launches
+        if fused_rnn_fp32:
+            if amp:
+                raise ValueError("fused_rnn_fp32=True is the float32 rollout's kernel: it needs amp=False")
+            zp = ac_policy.zero_vo_plan("x3") if hasattr(ac_policy, "zero_vo_plan") else None
+            if (not hasattr(ac_policy, "rnn_tiles_blob") or zp is None or ac_policy.rnn_tiles_blob("x3") is None
+                    or (env.W - zp["state_dim"]) % 9 or not 1 <= (env.W - zp["state_dim"]) // 9 <= 12):
+                raise ValueError("fused_rnn_fp32=True needs an rnn_ac with a shared GRU / biGRU reader of hidden 64 or "
+                                 "256, in_dim 9, state_dim <= 16, (256, 256) ReLU heads, on a GPU, and 1..12 VO slots")
+        self.fused_rnn_fp32 = bool(fused_rnn_fp32)
         # the advantages of RolloutBuffer.get() from ONE HIP launch (rvo3d_gae: the reference's recurrence, bit for bit,
         # no temporaries) instead of gae_scan's ~30 float64 tensor ops; any rollout mode, both update modes; a CPU
         # buffer ignores it.  Opt-in: advantages / returns differ from gae_scan's by a few float32 ulps, so switching
@@ -294,13 +306,16 @@ class multi_ppo:
         (256, 256) heads in reduced precision: rows without a velocity-obstacle row (nearly all) through the collapsed
         first layer, rvo3d_reader_zero_features + rvo3d_policy_mlp_sample, the others through the "heads" / "direct" path
         on a gathered batch; "rnn_tiles" - the same actor-critic with fused_rnn_tiles=True: the "rnn0" launches with the
-        rows that do have VO rows in 32-row MFMA tiles (rvo3d_policy_rnn_tiles), at any density; "direct" - any other
+        rows that do have VO rows in 32-row MFMA tiles (rvo3d_policy_rnn_tiles), at any density; "rnn_tiles_x3" - that mode's launches in a float32 rollout (amp=False,
+        fused_rnn_fp32=True) on the float32-class kernels rvo3d_policy_mlp_x3_sample / rvo3d_policy_rnn_tiles_x3; "direct" - any other
         actor-critic with the reference's surface (`ac.pi._distribution`, `ac.v`, e.g. the biGRU rnn_ac): its own forward
         gives mu and v, the kernel samples / rounds / stores; None - the module path of collect() (CPU, or fused_rollout=False)."""
         if self.device.type != "cuda" or not self.fused_rollout:
             return None
         if self.amp and getattr(self, "fused_rnn_tiles", False):
             return "rnn_tiles"
+        if not self.amp and getattr(self, "fused_rnn_fp32", False):
+            return "rnn_tiles_x3"
         if self.amp and self.fused_mlp and hasattr(self.ac, "mlp_blob") and self.ac.mlp_blob() is not None:
             return "mlp"
         if (not self.amp and self.fused_mlp and self.fused_mlp_fp32 and hasattr(self.ac, "mlp_blob")
@@ -367,7 +382,7 @@ class multi_ppo:
         (heads, tanh, sample, log-probability, np.round(a, 2), the three buffer stores), the env step from
         the stored action, rvo3d_rollout_account (reward slot, episode counters, path cuts, who still
         needs a reset).  Same semantics as collect(): multi_ppo.py:183-281.  graph_rollout=True replays the
-        "mlp" and "rnn0" modes only; every other mode ("mlp_x3" included) launches eagerly."""
+        "mlp" and "rnn0" modes only; every other mode ("mlp_x3" and "rnn_tiles_x3" included) launches eagerly."""
         import ctypes as C
         from .. import _lib
         env, buf, L = self.env, self.buf, _lib.lib()
@@ -392,8 +407,12 @@ class multi_ppo:
         log_std = self.ac.log_std
         # (once per rollout: the weights do not change inside it)
         mb = self.ac.mlp_blob() if mode == "mlp" else self.ac.mlp_blob("x3") if mode == "mlp_x3" else None
-        zp = self.ac.zero_vo_plan() if mode in ("rnn0", "rnn_tiles") else None
-        tb = self.ac.rnn_tiles_blob() if mode == "rnn_tiles" else None
+        x3 = mode == "rnn_tiles_x3"
+        zp = self.ac.zero_vo_plan("x3" if x3 else "bf16") if mode in ("rnn0", "rnn_tiles", "rnn_tiles_x3") else None
+        tb = self.ac.rnn_tiles_blob("x3" if x3 else "bf16") if mode in ("rnn_tiles", "rnn_tiles_x3") else None
+        # the two kernels behind rvo3d_reader_zero_features, by precision
+        zero_mlp, tiles = ("rvo3d_policy_mlp_x3_sample", "rvo3d_policy_rnn_tiles_x3") if x3 else \
+            ("rvo3d_policy_mlp_sample", "rvo3d_policy_rnn_tiles")
         plan = self.ac.fused_plan(dt) if mode == "heads" else None
         if zp is not None:
             # the scratch of the rnn modes, kept across rollouts (graph replay needs fixed addresses)
@@ -459,15 +478,14 @@ class multi_ppo:
                                                     p(zp["ln_w"]), p(zp["ln_b"]), zp["sum_h0"], zp["sumsq_h0"],
                                                     zp["eps"], p(f0), f0.stride(0), p(cnt), p(ac["vo_list"]),
                                                     p(vo_count), stream()), "rvo3d_reader_zero_features")
-            _lib.check(L.rvo3d_policy_mlp_sample(p(zp["blob"]), zp["width"], p(f0), f0.stride(0), E * N, None, 0, 0,
-                                                 1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
-                                                 step_arg(), *out, None, None, stream()), "rvo3d_policy_mlp_sample")
+            _lib.check(getattr(L, zero_mlp)(p(zp["blob"]), zp["width"], p(f0), f0.stride(0), E * N, None, 0, 0,
+                                            1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
+                                            step_arg(), *out, None, None, stream()), zero_mlp)
             if tb is not None:
-                _lib.check(L.rvo3d_policy_rnn_tiles(
+                _lib.check(getattr(L, tiles)(
                     p(tb["blob"]), tb["blob_bytes"], tb["hidden"], tb["in_dim"], tb["state_dim"], tb["bidir"], p(x),
                     x.stride(0), p(cnt), p(ac["vo_list"]), p(vo_count), done_blocks, p(ac["tiles_work"]), E * N, slots,
-                    1 if tb["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(), *out, None, stream()),
-                    "rvo3d_policy_rnn_tiles")
+                    1 if tb["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(), *out, None, stream()), tiles)
             else:
                 _lib.check(L.rvo3d_policy_rows(C.byref(zp["rows_net"]), p(x), x.stride(0), p(cnt), p(ac["vo_list"]),
                                                p(vo_count), done_blocks, 1 if zp["tanh"] else 0, p(log_std), 1.0,
@@ -495,7 +513,7 @@ class multi_ppo:
                                              stream()), "rvo3d_policy_sample")
 
         policy = {"mlp": policy_mlp, "mlp_x3": policy_mlp, "rnn0": policy_rnn0, "rnn_tiles": policy_rnn0,
-                  "direct": policy_direct, "heads": policy_heads}[mode]
+                  "rnn_tiles_x3": policy_rnn0, "direct": policy_direct, "heads": policy_heads}[mode]
 
         def launches(t, epoch_ended):
             policy(buf.obs[t].view(E * N, env.W), buf.cnt[t], (p(buf.act[t]), p(buf.logp[t]), p(buf.val[t])))

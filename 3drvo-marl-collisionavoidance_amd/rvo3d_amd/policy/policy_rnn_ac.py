@@ -410,14 +410,21 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
             return plan
         return _plan_cached(self, "_plan", list(self.parameters()), build, tag=dtype)
 
-    def zero_vo_plan(self):
+    def zero_vo_plan(self, precision="bf16"):
         """Weights for the rollout's fastest path (multi_ppo._collect_fused, mode "rnn0"): rows WITHOUT a velocity-obstacle
         row - nearly all of a rollout - all share the GRU's hidden state h0 (zero input from h = 0), so LayerNorm(concat(p,
         h0)) depends on a row through mean and rstd only and the first MLP layer collapses to a product over
         state_dim + 3 inputs (include/rvo3d.h, rvo3d_reader_zero_features): the whole policy step of such rows is then
         rvo3d_reader_zero_features + rvo3d_policy_mlp_sample.  Returns dict(blob, width, sum_h0, sumsq_h0, ln_w, ln_b,
         eps, feat_dim, tanh), rebuilt when a parameter changed; None when the architecture does not fit (LSTM or separate
-        readers, heads other than ReLU (256, 256) stacks, not on a GPU)."""
+        readers, heads other than ReLU (256, 256) stacks, not on a GPU).
+        precision="x3": the same plan for rvo3d_policy_mlp_x3_sample (float32-class products), in its own cache entry.
+        rvo3d_reader_zero_features' eight tail inputs - head(rstd), head(rstd), rstd - head, the same three of
+        mean rstd, 1, 1 - then take the float32 columns [a, 0, a | -b, 0, -b | c32, c - c32] and a zero bias: that
+        kernel splits its inputs itself, so rstd and mean rstd enter at full float32 precision.  No rows_net."""
+        if precision not in ("bf16", "x3"):
+            raise ValueError(f"precision must be 'bf16' or 'x3', not {precision!r}")
+        x3 = precision == "x3"
         r = self._gru_reader()
         if (r is None or r.state_dim > 16 or r.hidden_dim > 256 or r.input_dim > 16
                 or next(self.parameters()).device.type != "cuda"):
@@ -444,20 +451,22 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
                     cols = [Wp.float()]
                     for vec, sign in ((a, 1.0), (b, -1.0)):
                         v = (sign * vec).float()
-                        cols += [head(v)[:, None], (v - head(v))[:, None], head(v)[:, None]]
+                        cols += [v[:, None], torch.zeros_like(v)[:, None], v[:, None]] if x3 else \
+                            [head(v)[:, None], (v - head(v))[:, None], head(v)[:, None]]
                     cf = c.float()
-                    cols += [head(cf)[:, None], (cf - head(cf))[:, None]]
+                    cols += [cf[:, None], (c - cf.double()).float()[:, None]] if x3 else \
+                        [head(cf)[:, None], (cf - head(cf))[:, None]]
                     keep += [torch.cat(cols, 1).contiguous(), torch.zeros(256, device=dev),
                              l[1].weight.detach().float().contiguous(), l[1].bias.detach().float().contiguous(),
                              l[2].weight.detach().float().contiguous(), l[2].bias.detach().float().contiguous()]
-                blob = prev["blob"] if prev is not None else torch.empty(int(L.rvo3d_policy_mlp_blob_bytes(width)),
-                                                                         dtype=torch.uint8, device=dev)
+                nbytes, pack = (L.rvo3d_policy_mlp_x3_blob_bytes, "rvo3d_policy_mlp_x3_pack") if x3 else \
+                    (L.rvo3d_policy_mlp_blob_bytes, "rvo3d_policy_mlp_pack")
+                blob = prev["blob"] if prev is not None else torch.empty(int(nbytes(width)), dtype=torch.uint8, device=dev)
                 wa = _lib.MlpWeights(*[t.data_ptr() for t in keep[:6]])
                 wb = _lib.MlpWeights(*[t.data_ptr() for t in keep[6:]])
                 with torch.cuda.device(dev):
-                    _lib.check(L.rvo3d_policy_mlp_pack(C.byref(wa), C.byref(wb), width, C.c_void_p(blob.data_ptr()),
-                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                               "rvo3d_policy_mlp_pack")
+                    _lib.check(getattr(L, pack)(C.byref(wa), C.byref(wb), width, C.c_void_p(blob.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), pack)
                     torch.cuda.current_stream(dev).synchronize()  # (the temporaries above die with this scope)
                 # the modules' own tensors for rvo3d_policy_rows (the rows that do have VO rows): live parameters, no copies
                 gp = lambda n: getattr(r.rnn_net, n).data_ptr()
@@ -470,19 +479,24 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
                     float(r.ln.eps), 0,
                     _lib.MlpWeights(*[t.data_ptr() for l in lins[0] for t in (l.weight, l.bias)]),
                     _lib.MlpWeights(*[t.data_ptr() for l in lins[1] for t in (l.weight, l.bias)]))
-                ok_rows = all(t.is_contiguous() and t.dtype == torch.float32 for t in params)
+                ok_rows = not x3 and all(t.is_contiguous() and t.dtype == torch.float32 for t in params)
                 return dict(blob=blob, width=width, sum_h0=float(h0.sum()), sumsq_h0=float((h0 * h0).sum()),
                             rows_net=rows_net if ok_rows else None,
                             ln_w=r.ln.weight.detach().float().contiguous(), ln_b=r.ln.bias.detach().float().contiguous(),
                             eps=float(r.ln.eps), feat_dim=D, state_dim=r.state_dim, tanh=isinstance(acts[0][-1], nn.Tanh))
-        return _plan_cached(self, "_zero_plan", params, build)
+        return _plan_cached(self, "_zero_plan_x3" if x3 else "_zero_plan", params, build)
 
-    def rnn_tiles_blob(self):
+    def rnn_tiles_blob(self, precision="bf16"):
         """The packed weights of rvo3d_policy_rnn_tiles (the policy step of the rows WITH velocity-obstacle rows in 32-row
         MFMA tiles: csrc/rvo3d_policy_rnn_tiles.hpp) with the shape that call needs: dict(blob, blob_bytes, hidden, in_dim,
         state_dim, bidir, tanh).  Its own cache entry, repacked when a parameter changed (version or storage); None when
         the architecture does not fit - a shared GRU / biGRU reader of hidden 64 or 256, in_dim 9, state_dim <= 16, ReLU
-        (256, 256) stacks with 3 (Tanh or Identity) / 1 outputs, float32 parameters on a GPU."""
+        (256, 256) stacks with 3 (Tanh or Identity) / 1 outputs, float32 parameters on a GPU.
+        precision="x3": the blob of rvo3d_policy_rnn_tiles_x3 (the stacks in split bf16 as well: float32-class), with
+        its own size and its own cache entry."""
+        if precision not in ("bf16", "x3"):
+            raise ValueError(f"precision must be 'bf16' or 'x3', not {precision!r}")
+        sfx = "_x3" if precision == "x3" else ""
         r = self._gru_reader()
         if (r is None or r.hidden_dim not in (64, 256) or r.input_dim != 9 or not 1 <= r.state_dim <= 16
                 or next(self.parameters()).device.type != "cuda"):
@@ -499,7 +513,8 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
             from .. import _lib
             L = _lib.lib()
             bi = r.mode == "biGRU"
-            nbytes = int(L.rvo3d_policy_rnn_tiles_blob_bytes(r.hidden_dim, r.input_dim, r.state_dim, 1 if bi else 0))
+            nbytes = int(getattr(L, f"rvo3d_policy_rnn_tiles{sfx}_blob_bytes")(r.hidden_dim, r.input_dim, r.state_dim,
+                                                                               1 if bi else 0))
             dev = params[0].device
             blob = prev["blob"] if prev is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
             g = r.rnn_net
@@ -515,12 +530,13 @@ class rnn_ac(nn.Module):  # policy_rnn_ac.py:31-72
                                  _lib.MlpWeights(*[t.data_ptr() for t in heads[6:]]))
             with torch.cuda.device(dev):
                 st = torch.cuda.current_stream(dev)
-                _lib.check(L.rvo3d_policy_rnn_tiles_pack(C.byref(net), C.c_void_p(blob.data_ptr()), nbytes,
-                                                         C.c_void_p(st.cuda_stream)), "rvo3d_policy_rnn_tiles_pack")
+                pack = f"rvo3d_policy_rnn_tiles{sfx}_pack"
+                _lib.check(getattr(L, pack)(C.byref(net), C.c_void_p(blob.data_ptr()), nbytes, C.c_void_p(st.cuda_stream)),
+                           pack)
                 st.synchronize()  # (the contiguous copies above die with this scope)
             return dict(blob=blob, blob_bytes=nbytes, hidden=r.hidden_dim, in_dim=r.input_dim, state_dim=r.state_dim,
                         bidir=1 if bi else 0, tanh=isinstance(acts[0][-1], nn.Tanh))
-        return _plan_cached(self, "_tiles_blob", params, build)
+        return _plan_cached(self, "_tiles_blob" + sfx, params, build)
 
     def prepare_input(self, obs, cnt, plan, cache):
         """The reader's features [rows, Kp] as the A operand of the first MLP layer: rvo3d_reader_first_step for every

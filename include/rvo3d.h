@@ -294,6 +294,29 @@ int rvo3d_policy_rnn_tiles(const void *blob, int64_t blob_bytes, int32_t hidden,
                            int32_t tanh_out, const float *log_std, float std_factor, uint64_t seed, uint64_t step,
                            float *act, float *logp, float *val, float *dbg_mu, void *stream);
 
+/* The float32-class twin of the trio above (train/policy/policy_rnn_ac.py:57-69, :75-168, :197-257, float32) for float32
+ * rollouts and evaluations of the biGRU actor-critic.  Precision model: EVERY product - W_ih x, W_hh h, and here also the
+ * three layers of both stacks - is a_hi b_hi + a_hi b_lo + a_lo b_hi of bf16 halves (hi = bf16_rne(x), lo = bf16_rne(x -
+ * hi)) with float32 accumulation in one fixed order, so a row's result does not depend on its tile mates; the LayerNorm
+ * output and the ReLU'd float32 sums of both hidden layers are split after they are formed; b1 / b2 initialise the float32
+ * accumulators, the head biases are added in float32; gate math, LayerNorm and the hidden state are float32.  Against a
+ * float64 forward of the modules mu (before the tanh) stays within 1e-4 (mean 1e-5) and v within 1e-4 relative, where the
+ * bf16 stacks of rvo3d_policy_rnn_tiles are 1e-3 off.  The noise is that of every other sampling entry point for the same
+ * (seed, step): Philox4x32-10 with counter (row, step), the same per-row tail.  Arguments, their checks (all before the
+ * first HIP call) and error texts, the list / count / done_blocks / work contract and rvo3d_policy_rnn_tiles_work_bytes
+ * are the bf16 trio's.  Blob rules: the blob has its own layout (the stacks' weights as hi and lo fragments), its own
+ * magic word and its own, larger size, rvo3d_policy_rnn_tiles_x3_blob_bytes (-1 for the shapes the bf16 query refuses);
+ * repack after every optimizer step.  Each call checks blob_bytes against ITS size for the shape - a blob of the other
+ * precision is refused with -1 before any launch - and each kernel the magic word and shape the blob records: a blob of
+ * the other precision or another shape computes nothing. */
+int64_t rvo3d_policy_rnn_tiles_x3_blob_bytes(int32_t hidden, int32_t in_dim, int32_t state_dim, int32_t bidir);
+int rvo3d_policy_rnn_tiles_x3_pack(const rvo3d_rnn_policy *net, void *blob, int64_t blob_bytes, void *stream);
+int rvo3d_policy_rnn_tiles_x3(const void *blob, int64_t blob_bytes, int32_t hidden, int32_t in_dim, int32_t state_dim,
+                              int32_t bidir, const float *obs, int64_t obs_ld, const int32_t *vo_count,
+                              const int32_t *list, int32_t *count, int32_t *done_blocks, int32_t *work, int64_t max_rows,
+                              int32_t slots, int32_t tanh_out, const float *log_std, float std_factor, uint64_t seed,
+                              uint64_t step, float *act, float *logp, float *val, float *dbg_mu, void *stream);
+
 /* Replaying a rollout step as a HIP graph.  The three (MLP policy) or five (biGRU policy) launches of a rollout step take
  * every argument by value, the noise counter `step` included: a captured graph would draw the same noise on every
  * replay.  With a device counter registered here (uint64 in device memory, or NULL to unregister; process-wide), every
