@@ -45,6 +45,8 @@ import numpy as np
 import torch
 from torch.optim import Adam
 
+from .policy_step import KernelPolicyStep
+
 
 def gae_scan(rew, val, cut, gamma=0.99, lam=0.97):
     """GAE over time, all columns at once.  rew, val: float [T, ...]; cut: bool [T, ...], True
@@ -202,36 +204,27 @@ class multi_ppo:
         self._order_rng = np.random.RandomState(seed)
         self.fused_rollout = bool(fused_rollout)
         # bf16 rollouts of the MLP(256, 256) actor-critic: the policy step as ONE matrix-core kernel
-        # (rvo3d_policy_mlp_sample) instead of cast + three library GEMMs + rvo3d_policy_sample
+        # (KernelPolicyStep "mlp") instead of cast + three library GEMMs + rvo3d_policy_sample
         self.fused_mlp = bool(fused_mlp)
         # float32 rollouts (amp=False) of the same actor-critic through the split-bf16 twin of that kernel
-        # (rvo3d_policy_mlp_x3_sample, float32-class products) instead of float32 GEMMs + rvo3d_policy_sample; opt-in
+        # ("mlp_x3", float32-class products) instead of float32 GEMMs + rvo3d_policy_sample; opt-in
         if amp and fused_mlp_fp32:
             raise ValueError("fused_mlp_fp32=True is the float32 rollout's kernel: it needs amp=False")
         self.fused_mlp_fp32 = bool(fused_mlp_fp32)
         # bf16 rollouts of the biGRU actor-critic in worlds where many drones have velocity-obstacle rows: mode
-        # "rnn_tiles" - the "rnn0" launches with the rows that have VO rows in 32-row MFMA tiles (rvo3d_policy_rnn_tiles)
-        # instead of one workgroup per row, whatever their density (no switch to "heads"); opt-in, eager launches only
+        # "rnn_tiles" - the "rnn0" launches with the rows that have VO rows in 32-row MFMA tiles instead of one workgroup
+        # per row, whatever their density (no switch to "heads"); opt-in, eager launches only
         if fused_rnn_tiles:
             if not amp:
                 raise ValueError("fused_rnn_tiles=True is a bf16 rollout kernel: it needs amp=True")
-            zp = ac_policy.zero_vo_plan() if hasattr(ac_policy, "zero_vo_plan") else None
-            if (not hasattr(ac_policy, "rnn_tiles_blob") or zp is None or ac_policy.rnn_tiles_blob() is None
-                    or (env.W - zp["state_dim"]) % 9 or not 1 <= (env.W - zp["state_dim"]) // 9 <= 12):
-                raise ValueError("fused_rnn_tiles=True needs an rnn_ac with a shared GRU / biGRU reader of hidden 64 or "
-                                 "256, in_dim 9, state_dim <= 16, (256, 256) ReLU heads, on a GPU, and 1..12 VO slots")
+            KernelPolicyStep.plans(ac_policy, "rnn_tiles", env.W, "fused_rnn_tiles=True")
         self.fused_rnn_tiles = bool(fused_rnn_tiles)
         # float32 rollouts (amp=False) of the same actor-critic: mode "rnn_tiles_x3" - the "rnn_tiles" launches on the
-        # float32-class kernels (the collapsed zero-VO layer through rvo3d_policy_mlp_x3_sample, the rows with VO rows
-        # through rvo3d_policy_rnn_tiles_x3) instead of the "heads" mode's float32 library GEMMs; opt-in, eager launches
+        # float32-class kernels instead of the "heads" mode's float32 library GEMMs; opt-in, eager launches
         if fused_rnn_fp32:
             if amp:
                 raise ValueError("fused_rnn_fp32=True is the float32 rollout's kernel: it needs amp=False")
-            zp = ac_policy.zero_vo_plan("x3") if hasattr(ac_policy, "zero_vo_plan") else None
-            if (not hasattr(ac_policy, "rnn_tiles_blob") or zp is None or ac_policy.rnn_tiles_blob("x3") is None
-                    or (env.W - zp["state_dim"]) % 9 or not 1 <= (env.W - zp["state_dim"]) // 9 <= 12):
-                raise ValueError("fused_rnn_fp32=True needs an rnn_ac with a shared GRU / biGRU reader of hidden 64 or "
-                                 "256, in_dim 9, state_dim <= 16, (256, 256) ReLU heads, on a GPU, and 1..12 VO slots")
+            KernelPolicyStep.plans(ac_policy, "rnn_tiles_x3", env.W, "fused_rnn_fp32=True")
         self.fused_rnn_fp32 = bool(fused_rnn_fp32)
         # the advantages of RolloutBuffer.get() from ONE HIP launch (rvo3d_gae: the reference's recurrence, bit for bit,
         # no temporaries) instead of gae_scan's ~30 float64 tensor ops; any rollout mode, both update modes; a CPU
@@ -298,31 +291,26 @@ class multi_ppo:
 
     # ---- rollout ------------------------------------------------------------------------
     def _fused_mode(self):
-        """How a rollout step runs on the GPU: "mlp" - config 3's MLP(256, 256) actor-critic in reduced precision:
-        the whole policy step (cast, hidden layers, heads, sampling, stores) is ONE kernel on the matrix cores,
-        rvo3d_policy_mlp_sample; "mlp_x3" - the same in a float32 rollout (amp=False, fused_mlp_fp32=True): the
-        split-bf16 kernel rvo3d_policy_mlp_x3_sample, float32-class products; "heads" - other MLP actor-critics (and float32): library GEMMs up to the last
-        hidden layers, everything from there on in rvo3d_policy_sample; "rnn0" - the reference's biGRU actor-critic with
-        (256, 256) heads in reduced precision: rows without a velocity-obstacle row (nearly all) through the collapsed
-        first layer, rvo3d_reader_zero_features + rvo3d_policy_mlp_sample, the others through the "heads" / "direct" path
-        on a gathered batch; "rnn_tiles" - the same actor-critic with fused_rnn_tiles=True: the "rnn0" launches with the
-        rows that do have VO rows in 32-row MFMA tiles (rvo3d_policy_rnn_tiles), at any density; "rnn_tiles_x3" - that mode's launches in a float32 rollout (amp=False,
-        fused_rnn_fp32=True) on the float32-class kernels rvo3d_policy_mlp_x3_sample / rvo3d_policy_rnn_tiles_x3; "direct" - any other
-        actor-critic with the reference's surface (`ac.pi._distribution`, `ac.v`, e.g. the biGRU rnn_ac): its own forward
-        gives mu and v, the kernel samples / rounds / stores; None - the module path of collect() (CPU, or fused_rollout=False)."""
+        """How a rollout step runs on the GPU.  A kind of KernelPolicyStep (policy_step.py describes their launches):
+        "mlp" / "mlp_x3" - config 3's MLP(256, 256) actor-critic in a bf16 / float32 (fused_mlp_fp32=True) rollout; "rnn0" -
+        the reference's biGRU actor-critic with (256, 256) heads in a bf16 rollout while few rows have VO rows;
+        "rnn_tiles" / "rnn_tiles_x3" - the same with fused_rnn_tiles=True (bf16) / fused_rnn_fp32=True (float32), at any
+        density.  Or a library-GEMM path: "heads" - other MLP actor-critics (and float32): GEMMs up to the last hidden
+        layers, everything from there on in rvo3d_policy_sample; "direct" - any other actor-critic with the reference's
+        surface (`ac.pi._distribution`, `ac.v`, e.g. the biGRU rnn_ac): its own forward gives mu and v, the kernel samples /
+        rounds / stores.  None - the module path of collect() (CPU, or fused_rollout=False)."""
         if self.device.type != "cuda" or not self.fused_rollout:
             return None
-        if self.amp and getattr(self, "fused_rnn_tiles", False):
+        fits = lambda kind: KernelPolicyStep.fits(self.ac, kind, self.env.W)
+        if self.amp and self.fused_rnn_tiles:
             return "rnn_tiles"
-        if not self.amp and getattr(self, "fused_rnn_fp32", False):
+        if not self.amp and self.fused_rnn_fp32:
             return "rnn_tiles_x3"
-        if self.amp and self.fused_mlp and hasattr(self.ac, "mlp_blob") and self.ac.mlp_blob() is not None:
+        if self.amp and self.fused_mlp and fits("mlp"):
             return "mlp"
-        if (not self.amp and self.fused_mlp and self.fused_mlp_fp32 and hasattr(self.ac, "mlp_blob")
-                and self.ac.mlp_blob("x3") is not None):
+        if not self.amp and self.fused_mlp and self.fused_mlp_fp32 and fits("mlp_x3"):
             return "mlp_x3"
-        if (self.amp and self.fused_mlp and not getattr(self, "_rnn0_dense", False) and hasattr(self.ac, "zero_vo_plan")
-                and self.ac.zero_vo_plan() is not None and self.ac.zero_vo_plan()["rows_net"] is not None):
+        if self.amp and self.fused_mlp and not getattr(self, "_rnn0_dense", False) and fits("rnn0"):
             return "rnn0"
         if hasattr(self.ac, "fused_plan"):
             plan = self.ac.fused_plan(torch.bfloat16 if self.amp else torch.float32)
@@ -377,12 +365,12 @@ class multi_ppo:
         return ctx()
 
     def _collect_fused(self, final_reset=True):
-        """collect() with the per-step glue on the device: per step ONE cast of the observation (bf16
-        rollouts), the policy GEMMs up to the last hidden layers (mlp_ac.hidden_pair), rvo3d_policy_sample
-        (heads, tanh, sample, log-probability, np.round(a, 2), the three buffer stores), the env step from
-        the stored action, rvo3d_rollout_account (reward slot, episode counters, path cuts, who still
-        needs a reset).  Same semantics as collect(): multi_ppo.py:183-281.  graph_rollout=True replays the
-        "mlp" and "rnn0" modes only; every other mode ("mlp_x3" and "rnn_tiles_x3" included) launches eagerly."""
+        """collect() with the per-step glue on the device: per step the policy part - the launches of a KernelPolicyStep
+        or, in the library-GEMM modes, ONE cast of the observation (bf16 rollouts), the policy GEMMs up to the last hidden
+        layers (mlp_ac.hidden_pair) and rvo3d_policy_sample (heads, tanh, sample, log-probability, np.round(a, 2), the
+        three buffer stores) - then the env step from the stored action and rvo3d_rollout_account (reward slot, episode
+        counters, path cuts, who still needs a reset).  Same semantics as collect(): multi_ppo.py:183-281.  graph_rollout=True
+        replays the "mlp" and "rnn0" modes only; every other mode ("mlp_x3" and "rnn_tiles_x3" included) launches eagerly."""
         import ctypes as C
         from .. import _lib
         env, buf, L = self.env, self.buf, _lib.lib()
@@ -405,32 +393,16 @@ class multi_ppo:
         since_full_reset = 0
         mode = self._fused_mode()
         log_std = self.ac.log_std
-        # (once per rollout: the weights do not change inside it)
-        mb = self.ac.mlp_blob() if mode == "mlp" else self.ac.mlp_blob("x3") if mode == "mlp_x3" else None
-        x3 = mode == "rnn_tiles_x3"
-        zp = self.ac.zero_vo_plan("x3" if x3 else "bf16") if mode in ("rnn0", "rnn_tiles", "rnn_tiles_x3") else None
-        tb = self.ac.rnn_tiles_blob("x3" if x3 else "bf16") if mode in ("rnn_tiles", "rnn_tiles_x3") else None
-        # the two kernels behind rvo3d_reader_zero_features, by precision
-        zero_mlp, tiles = ("rvo3d_policy_mlp_x3_sample", "rvo3d_policy_rnn_tiles_x3") if x3 else \
-            ("rvo3d_policy_mlp_sample", "rvo3d_policy_rnn_tiles")
         plan = self.ac.fused_plan(dt) if mode == "heads" else None
-        if zp is not None:
-            # the scratch of the rnn modes, kept across rollouts (graph replay needs fixed addresses)
-            slots = env.nm if hasattr(env, "nm") else (env.W - zp["state_dim"]) // 9
-            if mode == "rnn0":
-                zp["rows_net"].slots = slots
-            if "feat0" not in ac or ac["feat0"].shape != (E * N, zp["width"]):
-                ac["feat0"] = torch.empty((E * N, zp["width"]), dtype=torch.float32, device=self.device)
-                ac["vo_list"] = torch.zeros(E * N, dtype=torch.int32, device=self.device)
-                ac["vo_count"] = torch.zeros(2, dtype=torch.int32, device=self.device)   # [count, finished workgroups]
+        kernel_step = None
+        if mode in KernelPolicyStep.KINDS:  # one per mode, kept across rollouts: graph replay needs its scratch where it was
+            steps, key = ac.setdefault("policy_steps", {}), (mode, E * N)
+            kernel_step = steps.get(key)
+            if kernel_step is None:
+                kernel_step = steps[key] = KernelPolicyStep(self.ac, mode, env.W, E * N, option=f"rollout mode {mode!r}")
             else:
-                ac["vo_count"].zero_()  # (the kernels leave it at zero; a rollout that was interrupted half-way may not have)
-        if tb is not None:
-            nw = int(L.rvo3d_policy_rnn_tiles_work_bytes(E * N, slots)) // 4
-            if "tiles_work" not in ac or ac["tiles_work"].numel() != nw:
-                ac["tiles_work"] = torch.zeros(nw, dtype=torch.int32, device=self.device)
-            else:
-                ac["tiles_work"][:32].zero_()  # (the sub-lists' cursors: likewise)
+                kernel_step.clear()  # (a rollout that was interrupted half-way may have left its counters non-zero)
+            kernel_step.refresh()  # (once per rollout: the weights do not change inside it)
         # Graph replay (graph_rollout=True; the bf16 MLP and biGRU fast paths, "mlp" / "rnn0" only - "mlp_x3" and the
         # others always launch eagerly): the launches of step t - every argument by value,
         # every buffer slot at a fixed address - are captured once per slot into a HIP graph and replayed in later
@@ -458,45 +430,14 @@ class multi_ppo:
             _lib.check(L.rvo3d_rollout_set_step_counter(p(self._step_dev)), "rvo3d_rollout_set_step_counter")
         step_arg = lambda: (1 << 32) if (use_graph and not getattr(self, "_graph_failed", False)) else ac["step"]
 
-        # the policy part of a step, one function per mode: observation rows x, their VO counts cnt, the buffer slot's
-        # act / logp / val pointers out
-        def policy_mlp(x, cnt, out):
-            # (the env's counts: column groups that are zero for all rows of a wave are skipped)
-            name = "rvo3d_policy_mlp_sample" if mode == "mlp" else "rvo3d_policy_mlp_x3_sample"
-            _lib.check(getattr(L, name)(p(mb["blob"]), env.W, p(x), x.stride(0), E * N, p(cnt), 12, 9,
-                                        1 if mb["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(), *out,
-                                        None, None, stream()), name)
-
-        def policy_rnn0(x, cnt, out):
-            # rows without a velocity-obstacle row: collapsed first layer (rvo3d_reader_zero_features builds its 20
-            # inputs and lists the rows that do have VO rows) + the MFMA kernel; the listed rows: one workgroup each
-            # ("rnn0", as the modules compute them) or 32-row MFMA tiles grouped by their VO count on the device
-            # ("rnn_tiles"); no host synchronisation
-            f0, vo_count = ac["feat0"], ac["vo_count"]
-            done_blocks = C.c_void_p(vo_count.data_ptr() + 4)
-            _lib.check(L.rvo3d_reader_zero_features(p(x), x.stride(0), E * N, zp["state_dim"], zp["feat_dim"],
-                                                    p(zp["ln_w"]), p(zp["ln_b"]), zp["sum_h0"], zp["sumsq_h0"],
-                                                    zp["eps"], p(f0), f0.stride(0), p(cnt), p(ac["vo_list"]),
-                                                    p(vo_count), stream()), "rvo3d_reader_zero_features")
-            _lib.check(getattr(L, zero_mlp)(p(zp["blob"]), zp["width"], p(f0), f0.stride(0), E * N, None, 0, 0,
-                                            1 if zp["tanh"] else 0, p(log_std), 1.0, self._sample_seed,
-                                            step_arg(), *out, None, None, stream()), zero_mlp)
-            if tb is not None:
-                _lib.check(getattr(L, tiles)(
-                    p(tb["blob"]), tb["blob_bytes"], tb["hidden"], tb["in_dim"], tb["state_dim"], tb["bidir"], p(x),
-                    x.stride(0), p(cnt), p(ac["vo_list"]), p(vo_count), done_blocks, p(ac["tiles_work"]), E * N, slots,
-                    1 if tb["tanh"] else 0, p(log_std), 1.0, self._sample_seed, step_arg(), *out, None, stream()), tiles)
-            else:
-                _lib.check(L.rvo3d_policy_rows(C.byref(zp["rows_net"]), p(x), x.stride(0), p(cnt), p(ac["vo_list"]),
-                                               p(vo_count), done_blocks, 1 if zp["tanh"] else 0, p(log_std), 1.0,
-                                               self._sample_seed, step_arg(), *out, stream()), "rvo3d_policy_rows")
-
+        # the policy part of a step in the library-GEMM modes: observation rows x, their VO counts cnt, the buffer slot's
+        # act / logp / val out
         def policy_direct(x, cnt, out):
             mu, v = self._mu_v(x, cnt.view(E * N))
             hd = _lib.PolicyHeads(mu.data_ptr(), v.data_ptr(), mu.stride(0), 1, _lib.RVO3D_F32, 0, 0, 0,
                                   None, None, None, None, log_std.data_ptr())
-            _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"], *out, None, None,
-                                             stream()), "rvo3d_policy_sample")
+            _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"], *map(p, out), None,
+                                             None, stream()), "rvo3d_policy_sample")
 
         def policy_heads(x, cnt, out):
             # the first layer's A operand: mlp_ac - the observation cast into a zero-padded buffer (ONE kernel);
@@ -509,14 +450,14 @@ class multi_ppo:
                                   1 if plan["tanh"] else 0, 0, plan["w_pi"].data_ptr(), plan["b_pi"].data_ptr(),
                                   plan["w_v"].data_ptr(), plan["b_v"].data_ptr(), log_std.data_ptr())
             # (the generator's counter is (row, call number): every call draws fresh noise)
-            _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"], *out, None, None,
-                                             stream()), "rvo3d_policy_sample")
+            _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"], *map(p, out), None,
+                                             None, stream()), "rvo3d_policy_sample")
 
-        policy = {"mlp": policy_mlp, "mlp_x3": policy_mlp, "rnn0": policy_rnn0, "rnn_tiles": policy_rnn0,
-                  "rnn_tiles_x3": policy_rnn0, "direct": policy_direct, "heads": policy_heads}[mode]
+        policy = {"direct": policy_direct, "heads": policy_heads}.get(
+            mode, lambda x, cnt, out: kernel_step.launch(x, cnt, *out, 1.0, self._sample_seed, step_arg()))
 
         def launches(t, epoch_ended):
-            policy(buf.obs[t].view(E * N, env.W), buf.cnt[t], (p(buf.act[t]), p(buf.logp[t]), p(buf.val[t])))
+            policy(buf.obs[t].view(E * N, env.W), buf.cnt[t], (buf.act[t], buf.logp[t], buf.val[t]))
             ac["step"] += 1  # (the noise counter: one per step in every mode)
             # the env steps from the stored (rounded) action: rounding twice is rounding once
             env.step_policy(buf.act[t], autoreset=True, obs_out=buf.obs[t + 1], cnt_out=buf.cnt[t + 1])
@@ -531,7 +472,7 @@ class multi_ppo:
                 return launches(t, epoch_ended)
             key = (mode, t, bool(epoch_ended), T, buf.obs.data_ptr(), buf.act.data_ptr(), buf.logp.data_ptr(),
                    buf.val.data_ptr(), buf.rew.data_ptr(), buf.cnt.data_ptr(), ac["cut"].data_ptr(),
-                   (mb or zp)["blob"].data_ptr(), env.obs.data_ptr(), id(env))
+                   kernel_step.blob_ptr, env.obs.data_ptr(), id(env))
             g = self._graphs.get(key)
             if g is None:
                 if len(self._graphs) > 4 * T + 8:

@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .policy_step import KernelPolicyStep
 
 # bits of a record's flag byte (rvo3d_eval_account)
 REC_ARRIVED, REC_FINISHED, REC_COLLIDED, REC_TIMEOUT = 1, 2, 4, 8
@@ -83,11 +84,10 @@ class post_train:
     def __init__(self, env, num_episodes=100, max_ep_len=150, acceler_vel=1.0, render=False,
                  save=False, neighbor_region=4, neighbor_num=5, args=None, fused=False, policy_kernel=None,
                  poll_every=8, seed=0, **kwargs):
-        """fused: the device-side loop (module docstring); policy_kernel: None (policy.step_tensors), "mlp"
-        (rvo3d_policy_mlp_sample), "mlp_x3" (rvo3d_policy_mlp_x3_sample), "rnn_tiles" or "rnn_tiles_x3" (the biGRU
-        actor-critic's three launches, bf16 / float32-class: rvo3d_reader_zero_features, the collapsed zero-VO layer,
-        rvo3d_policy_rnn_tiles / _x3) - either loop; poll_every: steps between two host reads of the fused loop; seed:
-        of the kernels' counter-based noise."""
+        """fused: the device-side loop (module docstring); policy_kernel: None (policy.step_tensors) or the
+        KernelPolicyStep kind that runs the policy - "mlp", "mlp_x3" (the MLP actor-critic, bf16 / float32-class),
+        "rnn_tiles" or "rnn_tiles_x3" (the biGRU actor-critic, likewise) - either loop; poll_every: steps between two host
+        reads of the fused loop; seed: of the kernels' counter-based noise."""
         if policy_kernel not in (None, "mlp", "mlp_x3", "rnn_tiles", "rnn_tiles_x3"):
             raise ValueError("policy_kernel must be None, 'mlp', 'mlp_x3', 'rnn_tiles' or 'rnn_tiles_x3', "
                              f"not {policy_kernel!r}")
@@ -129,82 +129,18 @@ class post_train:
         return get_action
 
     def _kernel_policy(self, policy, std_factor):
-        """model.act as ONE kernel (policy_kernel "mlp": bf16 products, "mlp_x3": float32-class), on the packed
-        weights of `policy.mlp_blob`; noise from (seed, number of calls so far).  policy_kernel "rnn_tiles" /
-        "rnn_tiles_x3": the biGRU actor-critic's three launches (_rnn_kernel_policy)."""
+        """model.act as the launches of KernelPolicyStep(self.policy_kernel) - the trainer's, with the evaluator's
+        std_factor; noise from (seed, number of calls so far)."""
         env = self.env
-        if self.policy_kernel in ("rnn_tiles", "rnn_tiles_x3"):
-            return self._rnn_kernel_policy(policy, std_factor)
-        precision = "bf16" if self.policy_kernel == "mlp" else "x3"
-        blob_of = getattr(policy, "mlp_blob", None)
-        if blob_of is None or blob_of(precision) is None or getattr(policy, "obs_width", None) != env.W:
-            raise ValueError(f"policy_kernel={self.policy_kernel!r} needs an MLP(256, 256) actor-critic on the env's "
-                             "observation width (mlp_ac.mlp_blob returns its packed weights)")
-        L = _lib.lib()
-        fn = L.rvo3d_policy_mlp_sample if self.policy_kernel == "mlp" else L.rvo3d_policy_mlp_x3_sample
         rows = env.E * env.N
-        act = torch.empty((rows, 3), dtype=torch.float32, device=env.device)
-        logp = torch.empty(rows, dtype=torch.float32, device=env.device)   # scratch
-        val = torch.empty(rows, dtype=torch.float32, device=env.device)    # scratch
+        step = KernelPolicyStep(policy, self.policy_kernel, env.W, rows, option=f"policy_kernel={self.policy_kernel!r}")
+        f32 = dict(dtype=torch.float32, device=env.device)
+        act, logp, val = torch.empty((rows, 3), **f32), torch.empty(rows, **f32), torch.empty(rows, **f32)  # logp, val: scratch
         calls = [0]
-        p = lambda t: C.c_void_p(t.data_ptr())
 
         def get_action(obs, cnt):
-            mb = blob_of(precision)   # (cached; repacked when a parameter changed)
-            log_std = policy.log_std
-            _lib.check(fn(p(mb["blob"]), env.W, p(obs), obs.stride(0), rows, p(cnt), 12, 9, 1 if mb["tanh"] else 0,
-                          p(log_std), float(std_factor), self.seed, calls[0], p(act), p(logp), p(val), None, None,
-                          C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)), "rvo3d_policy_mlp_sample")
-            calls[0] += 1
-            return act
-
-        return get_action
-
-    def _rnn_kernel_policy(self, policy, std_factor):
-        """model.act of an rnn_ac as the trainer's "rnn_tiles" / "rnn_tiles_x3" launches with the evaluator's std_factor:
-        rvo3d_reader_zero_features (the collapsed layer's inputs of every row, the list of the rows with VO rows), the
-        collapsed zero-VO layer on the MLP kernel, the listed rows in 32-row tiles; on `policy.zero_vo_plan` /
-        `policy.rnn_tiles_blob` of that precision.  Owns the feature scratch, the list, its two counters and the work
-        area; noise from (seed, number of calls so far)."""
-        env = self.env
-        precision = "x3" if self.policy_kernel == "rnn_tiles_x3" else "bf16"
-        plans = (getattr(policy, "zero_vo_plan", None), getattr(policy, "rnn_tiles_blob", None))
-        zp0 = plans[0](precision) if plans[0] is not None else None
-        if (zp0 is None or plans[1](precision) is None or (env.W - zp0["state_dim"]) % 9
-                or not 1 <= (env.W - zp0["state_dim"]) // 9 <= 12):
-            raise ValueError(f"policy_kernel={self.policy_kernel!r} needs an rnn_ac with a shared GRU / biGRU reader of "
-                             "hidden 64 or 256, in_dim 9, state_dim <= 16, (256, 256) ReLU heads, on a GPU, and an env "
-                             "with 1..12 VO slots")
-        L = _lib.lib()
-        zero_mlp, tiles = ("rvo3d_policy_mlp_x3_sample", "rvo3d_policy_rnn_tiles_x3") if precision == "x3" else \
-            ("rvo3d_policy_mlp_sample", "rvo3d_policy_rnn_tiles")
-        rows, dev = env.E * env.N, env.device
-        slots = (env.W - zp0["state_dim"]) // 9
-        f32 = dict(dtype=torch.float32, device=dev)
-        act, logp, val = torch.empty((rows, 3), **f32), torch.empty(rows, **f32), torch.empty(rows, **f32)
-        feat = torch.empty((rows, zp0["width"]), **f32)
-        vo_list = torch.zeros(rows, dtype=torch.int32, device=dev)
-        ctr = torch.zeros(2, dtype=torch.int32, device=dev)   # [count, finished workgroups]
-        work = torch.zeros(int(L.rvo3d_policy_rnn_tiles_work_bytes(rows, slots)) // 4, dtype=torch.int32, device=dev)
-        calls = [0]
-        p = lambda t: C.c_void_p(t.data_ptr())
-
-        def get_action(obs, cnt):
-            zp, tb = plans[0](precision), plans[1](precision)   # (cached; repacked when a parameter changed)
-            log_std, tanh = policy.log_std, 1 if zp["tanh"] else 0
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            out = (p(act), p(logp), p(val))
-            _lib.check(L.rvo3d_reader_zero_features(p(obs), obs.stride(0), rows, zp["state_dim"], zp["feat_dim"],
-                                                    p(zp["ln_w"]), p(zp["ln_b"]), zp["sum_h0"], zp["sumsq_h0"], zp["eps"],
-                                                    p(feat), feat.stride(0), p(cnt), p(vo_list), p(ctr), st),
-                       "rvo3d_reader_zero_features")
-            _lib.check(getattr(L, zero_mlp)(p(zp["blob"]), zp["width"], p(feat), feat.stride(0), rows, None, 0, 0, tanh,
-                                            p(log_std), float(std_factor), self.seed, calls[0], *out, None, None, st),
-                       zero_mlp)
-            _lib.check(getattr(L, tiles)(p(tb["blob"]), tb["blob_bytes"], tb["hidden"], tb["in_dim"], tb["state_dim"],
-                                         tb["bidir"], p(obs), obs.stride(0), p(cnt), p(vo_list), p(ctr),
-                                         C.c_void_p(ctr.data_ptr() + 4), p(work), rows, slots, tanh, p(log_std),
-                                         float(std_factor), self.seed, calls[0], *out, None, st), tiles)
+            step.refresh()   # (cached; repacked when a parameter changed)
+            step.launch(obs, cnt, act, logp, val, float(std_factor), self.seed, calls[0])
             calls[0] += 1
             return act
 
@@ -226,8 +162,8 @@ class post_train:
         ep_len = torch.zeros(E, dtype=torch.int64, device=dev)
         ep_ret = torch.zeros(E, dtype=torch.float64, device=dev)
         speed_sum = torch.zeros(E, dtype=torch.float64, device=dev)
-        n = sn = 0
-        ep_len_list, mean_speed_list, ep_ret_list = [], [], []
+        n = 0
+        records = []   # (length, return, speed, flags) of every counted episode, in the order the loop meets them
         quota = -(-self.num_episodes // E)   # episodes counted per env
         counted = [0] * E
         total = quota * E
@@ -267,36 +203,25 @@ class post_train:
                     if counted[e] >= quota:
                         continue  # this env has delivered its share; it keeps stepping, uncounted
                     counted[e] += 1
-                    if ar[e]:
-                        ep_len_list.append(int(el[e]))
                     if self.inf_print:
                         print("%s, Episode %d \t EpRet %.3f \t EpLen %d \t EpSpeed  %.3f"
                               % ("Successful" if ar[e] else "Fail", n, er[e], el[e], sp[e]))
-                    ep_ret_list.append(float(er[e]))
-                    mean_speed_list.append(float(sp[e]))
+                    records.append((el[e], er[e], sp[e], (REC_ARRIVED if ar[e] else 0) | (REC_FINISHED if su[e] else 0)))
                     n += 1
-                    sn += int(su[e])
                 env.reset(ended)
                 obs, cnt = env.observe()
                 z = torch.zeros_like(ep_len)
                 ep_len = torch.where(ended, z, ep_len)
                 ep_ret = torch.where(ended, torch.zeros_like(ep_ret), ep_ret)
                 speed_sum = torch.where(ended, torch.zeros_like(speed_sum), speed_sum)
-        mean_len = 0 if not ep_len_list else np.round(np.mean(ep_len_list), 2)
-        std_len = 0 if not ep_len_list else np.round(np.std(ep_len_list), 2)
-        average_speed = np.round(np.mean(mean_speed_list), 2)
-        std_speed = np.round(np.std(mean_speed_list), 2)
-        line = ("policy_name: " + policy_name + "  successful rate: {:.2%}".format(sn / total)
-                + " average EpLen: %s std length %s average speed: %s std speed %s"
-                % (mean_len, std_len, average_speed, std_speed))
+        length, ret, speed, flags = zip(*records)
+        result, line, _ = summarize_records(np.arange(n), np.zeros(n, dtype=np.int64), length, ret, speed, flags, policy_name)
         if result_path is not None:
             with open(result_path + result_name, "a") as f:
                 print(line, file=f)
         if self.inf_print:
             print(line)
-        return dict(success_rate=sn / total, mean_len=float(mean_len), std_len=float(std_len),
-                    average_speed=float(average_speed), std_speed=float(std_speed),
-                    episodes=n, ep_ret=ep_ret_list, ep_len=ep_len_list, speed=mean_speed_list)
+        return result
 
     def _policy_test_fused(self, act_fn, policy_name, result_path, result_name):
         """The same evaluation with the episodes accounted for on the device (module docstring)."""

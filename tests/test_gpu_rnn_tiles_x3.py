@@ -273,7 +273,8 @@ def test_rnn_tiles_x3_mode_refuses_what_it_cannot_run():
 
 # ---- 7. the evaluator -------------------------------------------------------------------------------------------------
 def _three_launches(ac, precision, env, obs, cnt, std_factor, seed, step):
-    """The evaluator's policy step by hand: rvo3d_reader_zero_features, the collapsed layer, the tiles."""
+    """The evaluator's policy step by hand: rvo3d_reader_zero_features, the collapsed layer, the tiles.  Returns
+    ([act, logp, val], number of listed rows)."""
     L, rows = _lib.lib(), obs.shape[0]
     zp, tb = ac.zero_vo_plan(precision), ac.rnn_tiles_blob(precision)
     slots = (env.W - 12) // 9
@@ -296,7 +297,7 @@ def _three_launches(ac, precision, env, obs, cnt, std_factor, seed, step):
                                  _p(work), rows, slots, tanh, _p(ac.log_std), std_factor, seed, step, *o, None, _stream()),
                tiles)
     torch.cuda.synchronize()
-    return out[0], listed
+    return out, listed
 
 
 @pytest.mark.parametrize("kernel", ["rnn_tiles_x3", "rnn_tiles"])
@@ -327,7 +328,7 @@ def test_rnn_kernel_policy_in_both_loops(kernel):
     first = act_fn(obs, cnt).clone()
     second = act_fn(obs, cnt).clone()
     for step, want in ((0, first), (1, second)):
-        mine, listed = _three_launches(ac, precision, env, obs, cnt, 0.5, 11, step)
+        (mine, _, _), listed = _three_launches(ac, precision, env, obs, cnt, 0.5, 11, step)
         assert listed == int((cnt > 0).sum())
         assert torch.equal(mine.view(torch.int32), want.view(torch.int32)), step
     assert not torch.equal(first, second)    # (the call number is the noise step)

@@ -8,7 +8,7 @@ import gc
 import pytest
 import torch
 
-from rvo3d_amd.policy import mlp_ac, rnn_ac
+from rvo3d_amd.policy import KernelPolicyStep, mlp_ac, rnn_ac
 from rvo3d_amd.policy import policy_rnn_ac as P
 
 
@@ -215,3 +215,18 @@ def test_device_blobs_are_none_on_cpu_modules():
     with pytest.raises(ValueError):
         m.mlp_blob("fp8")
     assert m.fused_plan(torch.float32) is not None            # (the library-GEMM plan is plain tensors: any device)
+
+
+def test_kernel_policy_step_fits_no_cpu_module():
+    """The launcher's predicate is the models' own: nothing fits off the GPU, whatever the kind; a refusal starts with
+    the caller's words for what was asked; a kind that does not exist is an error, not a misfit."""
+    for ac, width in ((_mlp(), 30), (_rnn(), 102), (_rnn(mode="LSTM"), 102)):
+        for kind in KernelPolicyStep.KINDS:
+            assert KernelPolicyStep.fits(ac, kind, width) is False, kind
+            with pytest.raises(ValueError) as ex:
+                KernelPolicyStep(ac, kind, width, 64, option=f"policy_kernel={kind!r}")
+            assert str(ex.value).startswith(f"policy_kernel={kind!r} needs "), str(ex.value)
+        for call in (lambda: KernelPolicyStep.fits(ac, "gemm", width), lambda: KernelPolicyStep(ac, "gemm", width, 64)):
+            with pytest.raises(ValueError, match="kind must be one of"):
+                call()
+    assert set(KernelPolicyStep.KINDS) == {"mlp", "mlp_x3", "rnn0", "rnn_tiles", "rnn_tiles_x3"}
