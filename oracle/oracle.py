@@ -50,6 +50,7 @@ def lib():
         L.orc_set_state.argtypes = [vp] + [dp] * 7 + [ip, bp, bp]
         L.orc_des_vel.argtypes = [vp, dp]
         L.orc_rvo_vel.argtypes = [vp, dp, C.c_double, dp]
+        L.orc_get_rvo_branch.argtypes = [vp, ip, dp]
         L.orc_vo_inf.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, dp, ip]
         L.orc_get_margin.argtypes = [vp, dp, ip]
         L.orc_nan_count.restype = C.c_int64
@@ -77,6 +78,10 @@ def _ip(a):
 def _bp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
 
+
+# orc_get_rvo_branch (rvo3d_oracle.h): the path of an agent through vel_select, and the flag bits
+RVO_OUT_ONLY, RVO_OUT_SOME_IN, RVO_IN_ONLY, RVO_NONE = 0, 1, 2, 3
+RVO_OVERLAP, RVO_TC_ZERO = 4, 8
 
 STATE_FIELDS = ("pos", "vel", "yaw", "pitch", "real_len", "max_dev", "extra_len",
                 "wp_idx", "arrive", "dest")
@@ -188,6 +193,24 @@ class OracleEnv:
         vm = np.ascontiguousarray(vmax, dtype=np.float64)
         lib().orc_rvo_vel(self._h, _dp(vm), float(acceler), _dp(out))
         return out
+
+    def _rvo_record(self):
+        br, cs = np.zeros((self.E, self.N), np.int32), np.empty((self.E, self.N))
+        lib().orc_get_rvo_branch(self._h, _ip(br), _dp(cs))
+        return br, cs
+
+    def rvo_branch(self):
+        """Path of every agent through vel_select in the last rvo_vel call, [E, N] int32: RVO_OUT_ONLY,
+        RVO_OUT_SOME_IN, RVO_IN_ONLY or RVO_NONE."""
+        return self._rvo_record()[0] & 3
+
+    def rvo_flags(self):
+        """Flag bits of the last rvo_vel call, [E, N] int32: RVO_OVERLAP | RVO_TC_ZERO."""
+        return self._rvo_record()[0] & (RVO_OVERLAP | RVO_TC_ZERO)
+
+    def rvo_cs_near_one(self):
+        """Of every cs = cos(beta) the last rvo_vel call formed for the agent, the one nearest 1 (NaN: none)."""
+        return self._rvo_record()[1]
 
     def vo_inf(self, e, i, action):
         """rvo_inter.config_vo_inf for drone (e, i): (rows[k,9], flag, tmin, collision)."""

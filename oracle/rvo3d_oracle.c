@@ -56,6 +56,8 @@ struct orc_env {
   double *margin;     /* [E*N] min decision margin of the last call (audit) */
   int32_t *msite;     /* [E*N] source line of the decision that set it */
   uint8_t *vnoise;    /* [E*N] velocity came out of a cancelled speed (pure libm noise) */
+  int32_t *rvo_branch; /* [E*N] path of the last orc_rvo_vel through vel_select: ORC_RVO_* code | flag bits */
+  double *rvo_cs;      /* [E*N] of all cs = cos(beta) the last orc_rvo_vel formed for the agent, the one nearest 1 (NaN: none) */
 };
 
 /* ---- arithmetic primitives ------------------------------------------- */
@@ -670,6 +672,8 @@ orc_env *orc_create(int E, int N, int P, int nb, int nm, int env_train,
   h->arrive = (uint8_t *)calloc(G, 1);
   h->dest = (uint8_t *)calloc(G, 1);
   h->margin = (double *)calloc(G, sizeof(double));
+  h->rvo_branch = (int32_t *)calloc(G, sizeof(int32_t));
+  h->rvo_cs = (double *)calloc(G, sizeof(double));
   h->msite = (int32_t *)calloc(G, sizeof(int32_t));
   h->vnoise = (uint8_t *)calloc(G, 1);
   return h;
@@ -680,7 +684,8 @@ void orc_destroy(orc_env *h) {
   free(h->wp); free(h->n_points); free(h->route_len); free(h->radius); free(h->prio);
   free(h->bld); free(h->p); free(h->v); free(h->yaw); free(h->pitch);
   free(h->real_len); free(h->max_dev); free(h->extra_len); free(h->wp_idx);
-  free(h->arrive); free(h->dest); free(h->margin); free(h->msite); free(h->vnoise); free(h);
+  free(h->arrive); free(h->dest); free(h->margin); free(h->msite); free(h->vnoise);
+  free(h->rvo_branch); free(h->rvo_cs); free(h);
 }
 
 void orc_load_world(orc_env *h, const double *waypoints, const int32_t *n_points,
@@ -1004,11 +1009,14 @@ void orc_rvo_vel(const orc_env *h, const double *vmax, double acceler, double *o
     /* config_vo per neighbour (as intended): alpha, PAA, rel */
     double *vo = (double *)malloc(sizeof(double) * 7 * (size_t)(no > 0 ? no : 1));
     tl_margin = h->margin + g; tl_site = h->msite + g;
+    int32_t flags = 0;
+    double cs1 = NAN;
     for (int j = 0; j < no; ++j) {
       const double *o = odro + 8 * (size_t)j;
       double ab[3] = {o[0] - pa[0], o[1] - pa[1], o[2] - pa[2]};
       double q = (ra + o[6]) / norm3_blas(ab);
       double alpha = 1.57;
+      if (q > 1.0) flags |= ORC_RVO_OVERLAP;
       if (q <= 1.0) { double as = asin(q); mg_round0(as, 100.0); alpha = orc_py_round2(as); }  /* get_alpha */
       double pr = pra / (pra + o[7]);                                                          /* get_PAA */
       double *w = vo + 7 * (size_t)j;
@@ -1033,6 +1041,7 @@ void orc_rvo_vel(const orc_env *h, const double *vmax, double acceler, double *o
         double dotp = dot3_blas(w + 3, d3);
         double AB = norm3_blas(w + 3) * norm3_blas(d3);
         double cs = (AB != 0) ? dotp / AB : 0.0;
+        if (!(fabs(cs - 1) >= fabs(cs1 - 1))) cs1 = cs;  /* (record only) */
         double ang = acos(cs);
         mg_round0(ang, 100.0);
         if (w[6] > get_beta_classic(w + 3, d3)) in = 1;
@@ -1049,8 +1058,18 @@ void orc_rvo_vel(const orc_env *h, const double *vmax, double acceler, double *o
     if (sel_out >= 0) memcpy(o, cand + 3 * (size_t)sel_out, 3 * sizeof(double));
     else if (n_in > 0) memcpy(o, inside + 3 * (size_t)orc_rvo_select_inside(inside, n_in, agent, odro, no), 3 * sizeof(double));
     else o[0] = o[1] = o[2] = 0.0;
+    /* record only: which of vel_select's paths the agent took, and what decides its penalty */
+    if (no > 0 && rvo_tc_min(agent, odro, no) == 0) flags |= ORC_RVO_TC_ZERO;
+    h->rvo_branch[g] = flags | (sel_out >= 0 ? (n_in > 0 ? ORC_RVO_OUT_SOME_IN : ORC_RVO_OUT_ONLY)
+                                             : (n_in > 0 ? ORC_RVO_IN_ONLY : ORC_RVO_NONE));
+    h->rvo_cs[g] = cs1;
     free(others); free(keep); free(odro); free(vo);
   }
+}
+
+void orc_get_rvo_branch(const orc_env *h, int32_t *branch, double *cs_near_one) {
+  if (branch) memcpy(branch, h->rvo_branch, (size_t)h->E * h->N * sizeof(int32_t));
+  if (cs_near_one) memcpy(cs_near_one, h->rvo_cs, (size_t)h->E * h->N * sizeof(double));
 }
 
 void orc_vo_inf(orc_env *h, int e, int i, const double *action, double *rows,

@@ -79,6 +79,20 @@ void orc_des_vel(const orc_env *h, double *des_vel);
  * (reciprocal_vel_obs.py:19-166 as intended; the class itself cannot run: PARITY UNPINNED
  * for the driver loop, see the .c).  vmax[3], acceler; out [E*N][3]. */
 void orc_rvo_vel(const orc_env *h, const double *vmax, double acceler, double *out);
+/* Which path through vel_select each agent took in the LAST orc_rvo_vel call (a record for the tests: it
+ * changes nothing orc_rvo_vel computes).  branch [E][N] = one of the four codes, or-ed with the flag bits;
+ * cs_near_one [E][N] = of every cs = cos(beta) formed for the agent (candidate x kept neighbour) the one
+ * nearest 1, NaN if none was formed.  Either pointer may be NULL. */
+enum {
+  ORC_RVO_OUT_ONLY = 0,    /* an outside candidate won; no candidate was inside a velocity obstacle */
+  ORC_RVO_OUT_SOME_IN = 1, /* an outside candidate won; some candidates were inside                 */
+  ORC_RVO_IN_ONLY = 2,     /* every live candidate inside: the first minimum of the penalty won     */
+  ORC_RVO_NONE = 3,        /* no live candidate: velocity 0                                          */
+  ORC_RVO_CODE_MASK = 3,
+  ORC_RVO_OVERLAP = 4,     /* some kept neighbour overlaps (q > 1): get_alpha's alpha = 1.57 path   */
+  ORC_RVO_TC_ZERO = 8      /* tc_min == 0 over the kept neighbours: the penalty is infinite          */
+};
+void orc_get_rvo_branch(const orc_env *h, int32_t *branch, double *cs_near_one);
 /* The methods of reciprocal_vel_obs that run on an instance (reciprocal_vel_obs.py:32-54, :85-101
  * with an empty VO list, :119-124 with an empty vo_outside, :126-147, :149-151), call by call:
  * checked against tests/golden/rvo_calls.npz, which holds the reference's own return values. */
