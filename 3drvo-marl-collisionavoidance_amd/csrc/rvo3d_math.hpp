@@ -97,11 +97,12 @@ __device__ __forceinline__ double np_mod(double a, double b) {  // npy_divmod re
 // ulp, so when dif/|dif|*1000 is further than 1e-7 from a rounding tie the
 // rounded integers are the same and no trigonometry is needed; otherwise the
 // reference's exact sequence runs.
-__device__ __forceinline__ void des_vel(const Params& P, const double p[3], const double cur[3],
-                                        double out[3]) {
+// T04 = Cold::T04.  A caller that tests several points reads it once and passes the value: read inside the tests of
+// a short-circuit chain, each test fetched it again through a lane-predicated vector load (the step's integration).
+__device__ __forceinline__ void des_vel(double T04, const double p[3], const double cur[3], double out[3]) {
   const double dx = cur[0] - p[0], dy = cur[1] - p[1], dz = cur[2] - p[2];
   const double d2 = dot3b(dx, dy, dz, dx, dy, dz);
-  if (d2 > P.cold().T04) {  // norm > goal_threshold
+  if (d2 > T04) {  // norm > goal_threshold
     const double inv = 1000.0 / __builtin_sqrt(d2);
     const double ux = dx * inv, uy = dy * inv, uz = dz * inv;
     double kx = __builtin_rint(ux), ky = __builtin_rint(uy), kz = __builtin_rint(uz);
@@ -123,6 +124,10 @@ __device__ __forceinline__ void des_vel(const Params& P, const double p[3], cons
     out[0] = out[1] = out[2] = 0.0;
   }
 }
+__device__ __forceinline__ void des_vel(const Params& P, const double p[3], const double cur[3],
+                                        double out[3]) {
+  des_vel(P.cold().T04, p, cur, out);
+}
 
 // drone.calculate_deviation (drone.py:366-406)
 __device__ __forceinline__ double deviation(const double a[3], const double b[3],
@@ -137,9 +142,9 @@ __device__ __forceinline__ double deviation(const double a[3], const double b[3]
   return __builtin_sqrt(sq(p[0] - qx) + sq(p[1] - qy) + sq(p[2] - qz));
 }
 
-__device__ __forceinline__ bool arrived(const Params& P, const double p[3], const double d[3]) {
+__device__ __forceinline__ bool arrived(double T04, const double p[3], const double d[3]) {
   const double x = p[0] - d[0], y = p[1] - d[1], z = p[2] - d[2];
-  return dot3b(x, y, z, x, y, z) <= P.cold().T04;  // norm <= 0.4, drone.py:172
+  return dot3b(x, y, z, x, y, z) <= T04;  // norm <= 0.4, drone.py:172
 }
 
 // vel_obs3D.cal_vo_exp_tim (vel_obs3D.py:145-182)

@@ -444,10 +444,11 @@ __device__ __forceinline__ double mov_reward_k(const Params& P, bool collision, 
 
 enum Mode { kObserve = 0, kStep = 1, kStepAutoReset = 2 };
 
-// The old count of row g (consistent obs / vo_count pair, early_zero_blocks), clamped to nm (more only stores more).
-__device__ __forceinline__ uint32_t old_kept(const Params& P, int g) {
-  const uint32_t c = (uint32_t)P.prev_cnt[g];
-  return c < (uint32_t)P.nm ? c : (uint32_t)P.nm;
+// The old count of a row (consistent obs / vo_count pair, early_zero_blocks) as it is filed in L.kept: clamped to nm
+// (more only stores more; the clamp bounds what early_zero_blocks adds to a row's kept range).  The count itself is
+// requested raw, together with the loads around it: clamping at the load made it a round trip of its own.
+__device__ __forceinline__ int clamp_kept(const Params& P, uint32_t c) {
+  return (int)(c < (uint32_t)P.nm ? c : (uint32_t)P.nm);
 }
 
 // 128 VGPRs = 4 waves per SIMD.  One-wave workgroups (N <= 64): the 4096 waves of 64 x 4096 are
@@ -528,12 +529,19 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   //      state (waypoints, des_vel, deviation) is fetched after sweep A, which needs none of it
   uint32_t gw[NW];  // candidate words (stage G): on file from the previous step if it ended in this state
   const bool have_gw = MODE != kObserve && P.g_cached != 0;
-  // the old count of this drone's row (old_kept), read before anything of this step is stored.  One-wave
+  // the old count of this drone's row (clamp_kept), read before anything of this step is stored.  One-wave
   // workgroups read it here; several waves where the reset state is requested (one register less across the
   // sweeps: no spills there)
   uint32_t old_cnt = 0;
+  // ONE batch of loads: old count, record, stage-G words, action - no address depends on a loaded value, and
+  // nothing is computed from any of them before the last is requested (at the start of the kernel no other wave
+  // has work to hide a round trip behind).  The action arrives as it was passed, in variables of its own per type:
+  // a policy increment is float32, an absolute action float32 or float64.
+  const bool act_f64 = P.action_mode != 1 && P.action_f64 != 0;
+  float af[3] = {0.f, 0.f, 0.f};
+  double ad[3] = {0, 0, 0};
   if (active) {
-    if (LITE && NW == 1 && P.prev_cnt) old_cnt = old_kept(P, g);
+    if (LITE && NW == 1 && P.prev_cnt) old_cnt = (uint32_t)P.prev_cnt[g];  // raw: clamped where it is filed (clamp_kept)
     S.x = P.px()[g]; S.y = P.py()[g]; S.z = P.pz()[g];
     S.vx = P.vx()[g]; S.vy = P.vy()[g]; S.vz = P.vz()[g];
     if (P.uniform_rp) { S.r = P.r0; S.prio = P.prio0; }
@@ -543,30 +551,32 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
       for (int w = 0; w < NW; ++w) gw[w] = P.gcache(w)[g];
     }
     if (MODE != kObserve) {
+      if (act_f64) {
+        const double* A = static_cast<const double*>(P.actions) + (size_t)g * 3;
+        ad[0] = A[0]; ad[1] = A[1]; ad[2] = A[2];
+      } else {
+        const float* A = static_cast<const float*>(P.actions) + (size_t)g * 3;
+        af[0] = A[0]; af[1] = A[1]; af[2] = A[2];
+      }
       if (P.action_mode == 1) {
         // The trainer's glue (multi_ppo.py:196-205), in numpy's own types:
         //   a_inc = np.round(sample, 2)                  float32: rint(a * 100f) / 100f
         //   abs   = np.round(acceler * a_inc + vel, 2)   float32 product, widened, + float64
-        const float* A = static_cast<const float*>(P.actions) + (size_t)g * 3;
         const double vv[3] = {S.vx, S.vy, S.vz};
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          const float r = __builtin_rintf(A[k] * 100.0f) / 100.0f;
+          const float r = __builtin_rintf(af[k] * 100.0f) / 100.0f;
           const double x = (double)(P.acceler * r) + vv[k];
           a[k] = __builtin_rint(x * 100.0) / 100.0;
         }
       } else {
-        if (P.action_f64) {
-          const double* A = static_cast<const double*>(P.actions) + (size_t)g * 3;
-          a[0] = A[0]; a[1] = A[1]; a[2] = A[2];
-        } else {
-          const float* A = static_cast<const float*>(P.actions) + (size_t)g * 3;
-          a[0] = (double)A[0]; a[1] = (double)A[1]; a[2] = (double)A[2];
-        }
-        if (P.cold().act_scale > 0) {
-          a[0] = __builtin_rint(a[0] * P.cold().act_scale) / P.cold().act_scale;
-          a[1] = __builtin_rint(a[1] * P.cold().act_scale) / P.cold().act_scale;
-          a[2] = __builtin_rint(a[2] * P.cold().act_scale) / P.cold().act_scale;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a[k] = act_f64 ? ad[k] : (double)af[k];
+        const double act_scale = P.cold().act_scale;
+        if (act_scale > 0) {
+          a[0] = __builtin_rint(a[0] * act_scale) / act_scale;
+          a[1] = __builtin_rint(a[1] * act_scale) / act_scale;
+          a[2] = __builtin_rint(a[2] * act_scale) / act_scale;
         }
       }
     }
@@ -580,7 +590,7 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
   if (LITE && NW > 1 && tid == 0) *L.any_old = 0;
   L.kept[tid] = 0;
   __syncthreads();  // flags zeroed before anyone raises them
-  if (LITE && NW == 1 && active && P.prev_cnt) L.kept[lrow] = (int)old_cnt;  // until the rows are staged
+  if (LITE && NW == 1 && active && P.prev_cnt) L.kept[lrow] = clamp_kept(P, old_cnt);  // until the rows are staged
   L.x[tid] = S.x; L.y[tid] = S.y; L.z[tid] = S.z;
   L.vx[tid] = S.vx; L.vy[tid] = S.vy; L.vz[tid] = S.vz;
   L.r[tid] = S.r; L.prio[tid] = S.prio;
@@ -707,11 +717,12 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     S.vx = nvx; S.vy = nvy; S.vz = nvz;
     real_len = real_len + norm3b(S.x - q0, S.y - q1, S.z - q2);
     const double p[3] = {S.x, S.y, S.z};
+    const double T04 = P.cold().T04;  // one read for the arrival tests and des_vel below (rvo3d_math.hpp)
     // the destination matters only next to a waypoint: fetched on demand (rare)
     double dst[3] = {0, 0, 0};
-    if (f_arrive || arrived(P, p, cur)) load_wp(P, g, npts - 1, dst);
-    if (arrived(P, p, cur)) {  // drone.py:116-129
-      const bool at_dst = arrived(P, p, dst);
+    if (f_arrive || arrived(T04, p, cur)) load_wp(P, g, npts - 1, dst);
+    if (arrived(T04, p, cur)) {  // drone.py:116-129
+      const bool at_dst = arrived(T04, p, dst);
       if (at_dst) { extra_len = real_len - route_len; ex_set = true; }  // destination_arrive side effect
       if (!at_dst && wpi < npts - 1) {
         wpi += 1;
@@ -723,15 +734,15 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
       }
     }
     // dronestate on the post-move state
-    des_vel(P, p, cur, dv);
+    des_vel(T04, p, cur, dv);
     dev = deviation(prev, cur, p);
     if (dev > max_dev) max_dev = dev;
     // arrival flags (ir_gym.py:168-181)
     bool arrive_r = false, dest_r = false;
     const int waypoint_num = wpi;
-    if (!f_arrive && arrived(P, p, cur)) { f_arrive = true; arrive_r = true; }
+    if (!f_arrive && arrived(T04, p, cur)) { f_arrive = true; arrive_r = true; }
     if (f_arrive) {
-      if (arrived(P, p, dst)) {
+      if (arrived(T04, p, dst)) {
         extra_len = real_len - route_len;
         ex_set = true;
         if (!f_dest) { f_dest = true; dest_r = true; }
@@ -741,8 +752,11 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     mov_nc = mov_reward_k(P, false, arrive_r, waypoint_num, npts - 1, dest_r, dev, exlen > 0,
                           exlen);
     RVO3D_STAMP(19);
+    // the map's bounds are launch constants: read once, here, ahead of the step's first store (scalar loads) - and
+    // tested with `|`: `||` made each bound a lane-predicated vector load with a round trip of its own
+    const double map_x = P.cold().map[0], map_y = P.cold().map[1], map_z = P.cold().map[2];
     collision = building_hit(P, S);
-    if (S.x < 0 || S.x > P.cold().map[0] || S.y < 0 || S.y > P.cold().map[1] || S.z < 0 || S.z > P.cold().map[2])
+    if ((S.x < 0) | (S.x > map_x) | (S.y < 0) | (S.y > map_y) | (S.z < 0) | (S.z > map_z))
       collision = true;  // drone.drone_out_map, drone.py:213-225
     // final for this step unless the drone is reset below
     P.yaw()[g] = yaw; P.pitch()[g] = pitch; P.real_len()[g] = real_len;
@@ -793,16 +807,18 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     // few thousand cycles of store issue and needs no data at all: the loads land meanwhile
     double p[3] = {0, 0, 0}, rcur[3] = {0, 0, 0}, rdev = 0.0;
     uint32_t rdv_a = 0, rdv_b = 0;
-    if (NW > 1 && active && P.prev_cnt) {  // (see phase 0; visible to early_zero_blocks behind the next barrier)
-      old_cnt = old_kept(P, g);
-      L.kept[lrow] = (int)old_cnt;
-      if (old_cnt != 0) *L.any_old = 1;
-    }
+    // (see phase 0; requested in one batch with the start state, filed behind it; visible to early_zero_blocks
+    // behind the next barrier)
+    if (NW > 1 && active && P.prev_cnt) old_cnt = (uint32_t)P.prev_cnt[g];
     if (do_reset) {  // (dronestate of the start state: static, tabulated by rvo3d_load_world, dv0_kernel)
       load_wp(P, g, 0, p);
       rdev = P.dev0()[g];
       load_wp(P, g, 1, rcur);
       rdv_a = P.dv0_a()[g]; rdv_b = P.dv0_b()[g];
+    }
+    if (NW > 1 && active && P.prev_cnt) {
+      L.kept[lrow] = clamp_kept(P, old_cnt);
+      if (old_cnt != 0) *L.any_old = 1;
     }
     RVO3D_STAMP(26);
     // (one-wave workgroups: 64 x 4096 -2 %; with several waves per workgroup the blocks go out right
@@ -810,11 +826,14 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     if (NW == 1 && two_phase_rows(P, row0, nrows, full_rows) && !RVO3D_ABLATED(16)) early_zero_blocks<NW>(P, L, tid, row0, nrows);
     RVO3D_STAMP(27);
     if (do_reset) {  // drone.reset (drone.py:270-291); extra_len survives
+      // (read here, not inside the rare branch below: a Cold read under a lane-dependent condition turns the
+      // restage's reads of cen[] / cmax into vector loads, which queue behind the twelve stores of this block)
+      const double T04r = P.cold().T04;
       S.x = p[0]; S.y = p[1]; S.z = p[2]; S.vx = S.vy = S.vz = 0.0;
       dev = rdev;
       cur[0] = rcur[0]; cur[1] = rcur[1]; cur[2] = rcur[2];
       if (!dv_decode(rdv_a, rdv_b, dv)) {
-        des_vel(P, p, cur, dv);
+        des_vel(T04r, p, cur, dv);
         dev = deviation(p, cur, p);  // previous_des = waypoints[0] = the start position
       }
       store3(P.cur(0), P.cur(1), P.cur(2), g, cur);
