@@ -64,6 +64,10 @@ struct rvo3d_env {
   bool dv_valid = false;  // dvk_a/dvk_b describe the current state (see Params::dv_cached)
   bool g_valid = false;   // gcache describes the current state (see Params::g_cached)
   rvo3d::Geometry geo{};  // threads, blocks, LDS bytes of the step's launch
+  // per-env building sets (rvo3d_set_env_buildings): one device allocation of records + cells while attached.  `cold`
+  // stays the shared list's description; the device copy of Cold is whichever of the two is in force.
+  void* env_bld = nullptr;
+  double rmax = 0.0;  // largest drone radius of the loaded world: the reach of the building lists
 };
 
 namespace {
@@ -472,6 +476,7 @@ int rvo3d_destroy(rvo3d_env* h) {
   DeviceGuard dg;
   (void)dg.enter(h->cfg.device);
   (void)hipDeviceSynchronize();
+  if (h->env_bld) (void)hipFree(h->env_bld);
   if (h->arena) (void)hipFree(h->arena);
   delete h;
   return RVO3D_OK;
@@ -494,6 +499,8 @@ int rvo3d_load_world(rvo3d_env* h, const double* waypoints, const int32_t* n_poi
   rvo3d::StagedWorld w;
   std::string err;
   if (int rc2 = rvo3d::stage_world(h->P, waypoints, n_points, radius, priority, w, err)) return fail(rc2, err);
+  // a new world drops per-env building sets: the shared list is in force again (their allocation goes at the end)
+  if (h->env_bld) HIP_TRY(hipMemcpyAsync((void*)P.cold_, &C, sizeof C, hipMemcpyHostToDevice, s));
   // [P][3] rows of EN doubles into arrays of stride S
   HIP_TRY(hipMemcpy2DAsync((void*)P.wp(0, 0), (size_t)P.S * 8, w.wp.data(), EN * 8, EN * 8,
                            (size_t)P.P * 3, hipMemcpyHostToDevice, s));
@@ -518,9 +525,61 @@ int rvo3d_load_world(rvo3d_env* h, const double* waypoints, const int32_t* n_poi
   hipLaunchKernelGGL(rvo3d::wpcache_kernel, dim3((unsigned)((EN + tb - 1) / tb)), dim3(tb), 0, s, P);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));  // the host staging vectors die here
+  if (h->env_bld) {
+    (void)hipFree(h->env_bld);
+    h->env_bld = nullptr;
+  }
+  h->rmax = rvo3d::largest_radius(w.rad);
   h->world_loaded = true;
   h->dv_valid = true;  // reset_kernel filed the des_vel of every start state
   h->g_valid = false;
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_set_env_buildings(rvo3d_env* h, const double* buildings, const int32_t* counts, int32_t nb_max, void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check, and all of the host's work, before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  const Params& P = h->P;
+  bool detach = false;
+  std::string err;
+  if (int rc = rvo3d::check_env_buildings(P.E, buildings, counts, nb_max, detach, err)) return fail(rc, err);
+  rvo3d::Cold C = h->cold;  // the shared list's; attached: nb_max records and a grid of its own per env
+  rvo3d::StagedEnvBuildings w;
+  size_t bld_bytes = 0, grid_bytes = 0;
+  if (!detach) {
+    rvo3d::env_grid_dims(&h->cfg, P.E, rvo3d::kEnvGridBudget, C);
+    C.nb = nb_max;
+    rvo3d::stage_env_buildings(C, P.E, buildings, counts, nb_max, h->rmax, w);
+    bld_bytes = align_up(w.bld.size() * 8, 256);
+    grid_bytes = w.grid.size() * 2;
+    C.bld_stride = (uint32_t)nb_max * 4u;
+    C.bgrid_stride = (uint32_t)((size_t)C.bgx * C.bgy * (rvo3d::kBgridK + 1));
+  }
+  DeviceGuard dg;
+  if (int rc = dg.enter(h->cfg.device)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  void* buf = nullptr;
+  if (!detach) {
+    HIP_TRY(hipMalloc(&buf, bld_bytes + (grid_bytes ? grid_bytes : 256)));
+    C.bld = static_cast<const double*>(buf);
+    C.bgrid = reinterpret_cast<const uint16_t*>(static_cast<char*>(buf) + bld_bytes);
+  }
+  // in stream order behind the steps already enqueued; the old sets are freed once nothing reads them
+  hipError_t e = hipSuccess;
+  if (!detach) e = hipMemcpyAsync(buf, w.bld.data(), w.bld.size() * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && grid_bytes)
+    e = hipMemcpyAsync(static_cast<char*>(buf) + bld_bytes, w.grid.data(), grid_bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync((void*)P.cold_, &C, sizeof C, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the host staging dies here
+  if (e != hipSuccess) {
+    if (buf) (void)hipFree(buf);
+    return fail(RVO3D_ERR_HIP, std::string("rvo3d_set_env_buildings: ") + hipGetErrorString(e));
+  }
+  if (h->env_bld) (void)hipFree(h->env_bld);
+  h->env_bld = buf;
   return RVO3D_OK;
   RVO3D_API_END
 }

@@ -232,6 +232,16 @@ inline int stage_world(Params& P, const double* waypoints, const int32_t* n_poin
   return RVO3D_OK;
 }
 
+// The largest drone radius of a handle, as the building lists' reach uses it.
+inline double largest_radius(const std::vector<double>& rad) {
+  double rmax = 0.0;
+  for (size_t g = 0; g < rad.size(); ++g) {
+    if (rad[g] != rad[g]) rmax = INFINITY;  // a NaN radius: no pruning beyond the gate
+    else if (rad[g] > rmax) rmax = rad[g];
+  }
+  return rmax;
+}
+
 // The per-cell building lists (C.bgx > 0), kBgridK + 1 u16 per cell.
 inline std::vector<uint16_t> build_building_grid(const Cold& C, const double* buildings, const std::vector<double>& rad) {
   // cell (ix, iy) = [ix*cs, (ix+1)*cs] x [iy*cs, (iy+1)*cs], widened by 1e-3 m (the device
@@ -239,15 +249,10 @@ inline std::vector<uint16_t> build_building_grid(const Cold& C, const double* bu
   // (clamped lookups); a building is listed where a drone inside the cell could hit it:
   // within the 5 m gate AND within (largest drone radius + building radius) of its axis
   // (rvo_inter.py:104, :207) - with 0.2 m drones that is 2 cells per building instead of 5
-  const size_t EN = rad.size();
   std::vector<uint16_t> grid;
   const int K = kBgridK;
   const double cs = 1.0 / C.bg_inv;
-  double rmax = 0.0;
-  for (size_t g = 0; g < EN; ++g) {
-    if (rad[g] != rad[g]) rmax = INFINITY;  // a NaN radius: no pruning beyond the gate
-    else if (rad[g] > rmax) rmax = rad[g];
-  }
+  const double rmax = largest_radius(rad);
   grid.assign((size_t)C.bgx * C.bgy * (K + 1), 0);
   for (int ix = 0; ix < C.bgx; ++ix)
     for (int iy = 0; iy < C.bgy; ++iy) {
@@ -271,6 +276,87 @@ inline std::vector<uint16_t> build_building_grid(const Cold& C, const double* bu
       cell[0] = overflow ? 0xffff : (uint16_t)n;
     }
   return grid;
+}
+
+// ---- per-env building sets (rvo3d_set_env_buildings) ----
+
+constexpr int kMaxBuildings = 0xfffe;                   // u16 list entries; 0xffff is the "test all" count
+constexpr size_t kBgridCellBytes = (kBgridK + 1) * 2;  // one cell: count + kBgridK indices
+constexpr size_t kEnvGridBudget = (size_t)64 << 20;    // the cells of all envs together
+
+// The argument checks of rvo3d_set_env_buildings.  detach: the call asks for the shared list again.
+inline int check_env_buildings(int E, const double* buildings, const int32_t* counts, int32_t nb_max, bool& detach,
+                               std::string& err) {
+  detach = false;
+  if (nb_max < 0) {
+    err = "nb_max must be >= 0";
+    return RVO3D_ERR_INVALID;
+  }
+  if (nb_max > kMaxBuildings) {
+    err = "nb_max must stay below 65535 (16-bit building indices)";
+    return RVO3D_ERR_INVALID;
+  }
+  if (!buildings || nb_max == 0) {
+    if (buildings == nullptr && nb_max > 0 && counts) {
+      err = "counts without buildings";
+      return RVO3D_ERR_INVALID;
+    }
+    detach = true;
+    return RVO3D_OK;
+  }
+  if (counts)
+    for (int e = 0; e < E; ++e)
+      if (counts[e] < 0 || counts[e] > nb_max) {
+        err = "counts entries must be in [0, nb_max]";
+        return RVO3D_ERR_INVALID;
+      }
+  return RVO3D_OK;
+}
+
+// Grid dimensions of the per-env lists: the shared path's (building_grid_dims) when E grids of them fit the
+// budget, else the cell size grows until they do - down to one cell per env, which is the floor (beyond
+// budget / 32 envs even that exceeds the budget).  Results do not depend on the dimensions: the lists are
+// conservative and an overflowing cell tests every building.
+inline void env_grid_dims(const rvo3d_config* cfg, int E, size_t budget, Cold& C) {
+  rvo3d_config c = *cfg;
+  c.num_buildings = 1;
+  building_grid_dims(&c, C);
+  if (C.bgx == 0) return;
+  const size_t cells_max = budget / (kBgridCellBytes * (size_t)E);
+  double cs = 1.0 / C.bg_inv;
+  while ((size_t)C.bgx * C.bgy > cells_max && (C.bgx > 1 || C.bgy > 1)) {
+    cs *= 1.125;
+    C.bgx = (int)std::ceil(cfg->map_size[0] / cs); C.bgy = (int)std::ceil(cfg->map_size[1] / cs);
+    if (C.bgx < 1) C.bgx = 1;
+    if (C.bgy < 1) C.bgy = 1;
+    C.bg_inv = 1.0 / cs;
+  }
+}
+
+// What rvo3d_set_env_buildings copies to the device: [E][nb_max][4] records - env e's unused records
+// counts[e] .. nb_max - 1 hold a building no drone can hit (h = -inf: `bh > z - 2` and `z <= bh` are false for
+// every z, NaN included) - and [E][bgx * bgy] cells, env e's being build_building_grid of its own list.
+// C: the handle's Cold with the dimensions of env_grid_dims; rmax: largest_radius of the loaded world.
+struct StagedEnvBuildings { std::vector<double> bld; std::vector<uint16_t> grid; };
+inline void stage_env_buildings(const Cold& C, int E, const double* buildings, const int32_t* counts, int32_t nb_max,
+                                double rmax, StagedEnvBuildings& out) {
+  const size_t rec = (size_t)nb_max * 4, cells = (size_t)C.bgx * C.bgy * (kBgridK + 1);
+  out.bld.assign((size_t)E * rec, 0.0);
+  out.grid.clear();
+  out.grid.reserve((size_t)E * cells);
+  const std::vector<double> rad(1, rmax);
+  Cold Ce = C;
+  for (int e = 0; e < E; ++e) {
+    const int n = counts ? counts[e] : nb_max;
+    double* dst = &out.bld[(size_t)e * rec];
+    std::memcpy(dst, buildings + (size_t)e * rec, (size_t)n * 32);
+    for (int b = n; b < nb_max; ++b) dst[4 * b + 2] = -INFINITY;
+    if (C.bgx > 0) {
+      Ce.nb = n;
+      const std::vector<uint16_t> g = build_building_grid(Ce, dst, rad);
+      out.grid.insert(out.grid.end(), g.begin(), g.end());
+    }
+  }
 }
 
 }  // namespace rvo3d

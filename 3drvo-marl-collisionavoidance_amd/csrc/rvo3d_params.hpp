@@ -46,6 +46,9 @@ struct Cold {
   const uint16_t* bgrid;
   int bgx, bgy;
   double bg_inv;           // 1 / cell size
+  // per-env building sets (rvo3d_set_env_buildings): env e reads bld + e * bld_stride (doubles) and
+  // bgrid + e * bgrid_stride (u16), nb is nb_max (unused records cannot be hit).  Both 0: the shared list.
+  uint32_t bld_stride, bgrid_stride;
 };
 constexpr int kBgridK = 15;
 typedef const __attribute__((address_space(4))) Cold ColdC;

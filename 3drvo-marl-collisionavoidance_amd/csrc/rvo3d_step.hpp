@@ -17,11 +17,13 @@ __device__ __forceinline__ bool building_test(const double* const bld, int b, co
     return __builtin_sqrt(sq(ex) + sq(ey)) <= S.r + br;
   return false;
 }
-__device__ __forceinline__ bool building_hit(const Params& P, const Drone& S) {
+// e: the drone's env (an active lane's: e < P.E).  Per-env sets (rvo3d_set_env_buildings) give the records and the
+// cells an element stride per env; with the shared list both strides are 0 and every env reads the one copy.
+__device__ __forceinline__ bool building_hit(const Params& P, const Drone& S, int e) {
   const int nb = P.cold().nb;
   if (nb == 0) return false;
   bool hit = false;
-  const double* const bld = P.cold().bld;
+  const double* const bld = P.cold().bld + (size_t)e * P.cold().bld_stride;
   const double T5 = P.cold().T5;
   const int gx = P.cold().bgx;
   if (gx > 0) {
@@ -35,7 +37,7 @@ __device__ __forceinline__ bool building_hit(const Params& P, const Drone& S) {
     // the count and the first seven entries in one 16-B load (lists are short: most cells have
     // none or one), the records of two listed buildings per round trip (entry 1 pads the batch:
     // testing a building twice changes nothing); longer lists are walked from memory
-    const uint16_t* const cell = P.cold().bgrid + (size_t)(ix * gy + iy) * (kBgridK + 1);
+    const uint16_t* const cell = P.cold().bgrid + (size_t)e * P.cold().bgrid_stride + (size_t)(ix * gy + iy) * (kBgridK + 1);
     const uint4 c0 = *reinterpret_cast<const uint4*>(cell);
     const int cnt = (int)(c0.x & 0xffffu);
     if (cnt != 0xffff) {
@@ -755,7 +757,7 @@ __global__ void __launch_bounds__(64 * NW) RVO3D_WAVES_ATTR env_kernel(const Par
     // the map's bounds are launch constants: read once, here, ahead of the step's first store (scalar loads) - and
     // tested with `|`: `||` made each bound a lane-predicated vector load with a round trip of its own
     const double map_x = P.cold().map[0], map_y = P.cold().map[1], map_z = P.cold().map[2];
-    collision = building_hit(P, S);
+    collision = building_hit(P, S, e);
     if ((S.x < 0) | (S.x > map_x) | (S.y < 0) | (S.y > map_y) | (S.z < 0) | (S.z > map_z))
       collision = true;  // drone.drone_out_map, drone.py:213-225
     // final for this step unless the drone is reset below

@@ -11,8 +11,9 @@ HIP extension is missing, and every compute call needs a GPU.
 """
 from ._lib import build_hip, lib, lib_path, RVO3DError  # noqa: F401
 from .batched_env import BatchedDroneEnv  # noqa: F401
-from .worlds import World, crossing_world, load_world_dir, synthetic_world, synthetic_actions  # noqa: F401
+from .worlds import (World, crossing_world, load_world_dir, stack_worlds, synthetic_world,  # noqa: F401
+                     synthetic_actions)
 from . import sharding  # noqa: F401
 
-__all__ = ["BatchedDroneEnv", "World", "crossing_world", "load_world_dir", "synthetic_world",
+__all__ = ["BatchedDroneEnv", "World", "crossing_world", "load_world_dir", "stack_worlds", "synthetic_world",
            "synthetic_actions", "build_hip", "lib", "lib_path", "RVO3DError"]

@@ -47,7 +47,9 @@ class BatchedDroneEnv:
         self.env_train = bool(env_train)  # rvo_inter.env_train (rvo_inter.py:14)
         self.world = world
         L = _lib.lib()
-        cfg = _lib.Config(self.E, self.N, self.P, int(world.buildings.shape[0]), self.nm,
+        # a set per env (World.buildings [E, nb_max, 4]): no shared list, the sets are attached after the world is loaded
+        per_env = world.per_env_buildings
+        cfg = _lib.Config(self.E, self.N, self.P, 0 if per_env else int(world.buildings.shape[0]), self.nm,
                           int(bool(env_train)), self.device.index or 0, int(action_decimals),
                           (C.c_double * 3)(*[float(x) for x in world.map_size]))
         h = C.c_void_p()
@@ -55,7 +57,7 @@ class BatchedDroneEnv:
         self._h = h
         wp = np.ascontiguousarray(world.waypoints, dtype=np.float64)
         npts = np.ascontiguousarray(world.n_points, dtype=np.int32)
-        bld = np.ascontiguousarray(world.buildings, dtype=np.float64)
+        bld = np.zeros((0, 4)) if per_env else np.ascontiguousarray(world.buildings, dtype=np.float64)
         rad = None if radius is None else np.ascontiguousarray(
             np.broadcast_to(np.asarray(radius, dtype=np.float64), (self.E, self.N)))
         pri = None if priority is None else np.ascontiguousarray(
@@ -64,6 +66,8 @@ class BatchedDroneEnv:
         with torch.cuda.device(self.device):
             _lib.check(L.rvo3d_load_world(h, hp(wp), hp(npts), hp(bld) if bld.size else None,
                                           hp(rad), hp(pri), self._stream()), "rvo3d_load_world")
+        if per_env:
+            self.set_env_buildings(world.buildings, world.building_counts)
         E, N, dev = self.E, self.N, self.device
         self.obs = torch.zeros((E, N, self.W), dtype=torch.float32, device=dev)
         self.vo_count = torch.zeros((E, N), dtype=torch.int32, device=dev)
@@ -99,6 +103,27 @@ class BatchedDroneEnv:
             self.close()
         except Exception:
             pass
+
+    def set_env_buildings(self, buildings, counts=None):
+        """A building set per env from the next step on (rvo3d_set_env_buildings): buildings [E, nb_max, 4] = x,y,h,r,
+        counts [E] (env e collides with buildings[e, :counts[e]]; None: all nb_max).  Replaces the sets in force, e.g.
+        to re-draw the cities between epochs; set_env_buildings(None) goes back to the world's shared list.
+        Synchronises the current stream."""
+        b = c = None
+        nb_max = 0
+        if buildings is not None:
+            b = np.ascontiguousarray(buildings, dtype=np.float64)
+            if b.ndim != 3 or b.shape[0] != self.E or b.shape[2] != 4:
+                raise AssertionError(f"buildings must have shape ({self.E}, nb_max, 4)")
+            nb_max = int(b.shape[1])
+            if counts is not None:
+                c = np.ascontiguousarray(counts, dtype=np.int32)
+                if c.shape != (self.E,):
+                    raise AssertionError(f"counts must have shape ({self.E},)")
+        hp = lambda a: None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().rvo3d_set_env_buildings(self._h, hp(b), hp(c), nb_max, self._stream()),
+                       "rvo3d_set_env_buildings")
 
     def _actions(self, actions):
         a = actions

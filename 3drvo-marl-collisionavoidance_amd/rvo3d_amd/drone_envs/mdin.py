@@ -57,7 +57,7 @@ class _IrGym:
         self.acceler = acceler
         self.nr, self.nm, self.env_train = neighbors_region, neighbors_num, env_train
         self.map_size = list(env.world.map_size)
-        self.building_list = env.world.buildings.tolist()
+        self.building_list = env.world.env_buildings(0).tolist()
         self.observation_space = _Box(-np.inf, np.inf, shape=(21,), dtype=np.float32)
         self.action_space = _Box(np.array([-1, -1, -1]), np.array([1, 1, 1]), dtype=np.float32)
         self.drone_list = [_DroneView(self, i) for i in range(env.N)]

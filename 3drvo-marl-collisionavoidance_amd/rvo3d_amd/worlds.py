@@ -11,15 +11,36 @@ import numpy as np
 
 @dataclass
 class World:
-    """Routes for E envs x N drones plus buildings shared by all envs."""
+    """Routes for E envs x N drones plus buildings: one list shared by all envs, or a set per env."""
     waypoints: np.ndarray          # [E, N, P, 3] float64 (padded with the destination)
     n_points: np.ndarray           # [E, N] int32
     map_size: np.ndarray           # [3]
-    buildings: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))  # [nb, 4] x,y,h,r
+    # [nb, 4] x,y,h,r shared by every env, or [E, nb_max, 4]: env e's own set
+    buildings: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))
+    # per-env sets only: [E] int32, env e's set is buildings[e, :building_counts[e]] (None: all nb_max)
+    building_counts: np.ndarray | None = None
 
     @property
     def shape(self):
         return self.waypoints.shape[:3]
+
+    @property
+    def per_env_buildings(self) -> bool:
+        return np.ndim(self.buildings) == 3
+
+    def env_buildings(self, e: int) -> np.ndarray:
+        """Env e's building list [n, 4], whether the world shares one list or holds a set per env."""
+        if not self.per_env_buildings:
+            return self.buildings
+        n = self.buildings.shape[1] if self.building_counts is None else int(self.building_counts[e])
+        return self.buildings[e, :n]
+
+    def select(self, envs) -> "World":
+        """The world of the listed envs (indices, a slice or a mask over E); a shared list stays shared."""
+        per = self.per_env_buildings
+        cnt = self.building_counts[envs] if per and self.building_counts is not None else None
+        return World(self.waypoints[envs], self.n_points[envs], self.map_size,
+                     self.buildings[envs] if per else self.buildings, cnt)
 
 
 def world_from_dict(d: dict, num_envs: int = 1) -> World:
@@ -46,11 +67,19 @@ def load_world_dir(base_dir: str, num_envs: int = 1) -> World:
         return world_from_dict(json.load(f), num_envs)
 
 
+def _draw_buildings(brng, nb: int, map_size) -> np.ndarray:
+    L, Wd, H = map_size
+    return np.round(np.stack([brng.uniform(2, L - 2, nb), brng.uniform(2, Wd - 2, nb),
+                              brng.uniform(3, H, nb), brng.uniform(0.5, 1.5, nb)], axis=1), 2)
+
+
 def synthetic_world(E: int, N: int, map_size, n_points: int = 2, nb: int = 0, seed: int = 1234,
-                    min_sep: float = 1.0) -> World:
+                    min_sep: float = 1.0, per_env_buildings: bool = False) -> World:
     """per env e, rng = Philox(seed, stream e); starts/ends
     ~U([1, L-1]^2 x [1, H-1]) rounded to 2 decimals, starts at least min_sep
-    apart; buildings [x,y ~U(2, L-2), h ~U(3, H), r ~U(0.5, 1.5)] shared."""
+    apart; buildings [x,y ~U(2, L-2), h ~U(3, H), r ~U(0.5, 1.5)] rounded to 2 decimals: one list
+    from Philox(seed + 1) shared by every env, or - per_env_buildings - env e's own nb buildings
+    from Philox(seed + 1, stream e) (env e's set does not depend on E)."""
     L, Wd, H = map_size
     lo = np.array([1.0, 1.0, 1.0])
     hi = np.array([L - 1.0, Wd - 1.0, H - 1.0])
@@ -65,11 +94,48 @@ def synthetic_world(E: int, N: int, map_size, n_points: int = 2, nb: int = 0, se
                 starts[i] = np.round(rng.uniform(lo, hi), 2)
                 tries += 1
         wp[e] = pts
-    brng = np.random.Generator(np.random.Philox(key=seed + 1))
-    bld = np.round(np.stack([brng.uniform(2, L - 2, nb), brng.uniform(2, Wd - 2, nb),
-                             brng.uniform(3, H, nb), brng.uniform(0.5, 1.5, nb)], axis=1), 2) \
-        if nb else np.zeros((0, 4))
+    if per_env_buildings:
+        bld = np.stack([_draw_buildings(np.random.Generator(np.random.Philox(key=seed + 1, counter=[0, 0, 0, e])),
+                                        nb, map_size) for e in range(E)])
+    else:
+        brng = np.random.Generator(np.random.Philox(key=seed + 1))
+        bld = _draw_buildings(brng, nb, map_size) if nb else np.zeros((0, 4))
     return World(wp, np.full((E, N), n_points, np.int32), np.asarray(map_size, dtype=np.float64), bld)
+
+
+def stack_worlds(worlds) -> World:
+    """One batch of several worlds, concatenated along E: equal drone counts and map sizes (ValueError otherwise),
+    shorter routes padded with the destination.  The buildings stay one shared list when every world brings the
+    same one; otherwise each env gets the list of the world it came from (building_counts where the lengths differ)."""
+    worlds = list(worlds)
+    if not worlds:
+        raise ValueError("stack_worlds needs at least one world")
+    N, m = worlds[0].shape[1], np.asarray(worlds[0].map_size, dtype=np.float64)
+    for w in worlds:
+        if w.shape[1] != N:
+            raise ValueError("stack_worlds: the worlds have different drone counts")
+        if not np.array_equal(np.asarray(w.map_size, dtype=np.float64), m):
+            raise ValueError("stack_worlds: the worlds have different map sizes")
+    P = max(w.shape[2] for w in worlds)
+    wps = []
+    for w in worlds:
+        wp = np.asarray(w.waypoints, dtype=np.float64)
+        E, p = wp.shape[0], wp.shape[2]
+        if p < P:  # pad with each drone's destination, wp[e, i, n_points - 1]
+            last = np.take_along_axis(wp, (np.asarray(w.n_points).astype(np.int64) - 1)[:, :, None, None], axis=2)
+            wp = np.concatenate([wp, np.broadcast_to(last, (E, N, P - p, 3))], axis=2)
+        wps.append(wp)
+    wp = np.concatenate(wps, 0)
+    npts = np.concatenate([np.asarray(w.n_points, dtype=np.int32) for w in worlds], 0)
+    lists = [np.asarray(w.env_buildings(e), dtype=np.float64).reshape(-1, 4) for w in worlds for e in range(w.shape[0])]
+    if all(l.shape == lists[0].shape and np.array_equal(l, lists[0]) for l in lists):
+        return World(wp, npts, m, lists[0].copy())
+    nb_max = max(len(l) for l in lists)
+    bld = np.zeros((len(lists), nb_max, 4))
+    for e, l in enumerate(lists):
+        bld[e, :len(l)] = l
+    cnt = np.asarray([len(l) for l in lists], dtype=np.int32)
+    return World(wp, npts, m, bld, None if np.all(cnt == nb_max) else cnt)
 
 
 def crossing_world(E: int, N: int, map_size, radius: float | None = None, alt_spread: float = 1.0,

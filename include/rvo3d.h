@@ -97,6 +97,16 @@ int rvo3d_load_world(rvo3d_env *h, const double *waypoints, const int32_t *n_poi
                      const double *buildings, const double *radius,
                      const double *priority, void *stream);
 
+/* Per-env building sets.  HOST pointers: buildings [E][nb_max][4] = x,y,h,r; counts [E] (each 0..nb_max; NULL = nb_max
+ * for every env).  From the next step on, env e collides with buildings[e][0 .. counts[e]) and with nothing else:
+ * exactly the env of a handle whose shared list (rvo3d_load_world) is that list.  The shared list is ignored while
+ * sets are attached.  buildings == NULL or nb_max == 0 detaches: back to the shared list.  Needs a loaded world
+ * (RVO3D_ERR_STATE otherwise: the lists' reach uses the drones' radii); a later rvo3d_load_world drops the sets.
+ * nb_max < 65535 (16-bit indices in the per-cell lists).  Allocates the handle-owned device copies here (freed by the
+ * next call / rvo3d_destroy) and synchronises; step and observe still allocate nothing.  Every argument check runs
+ * before the first HIP call; a refused call leaves the handle as it was. */
+int rvo3d_set_env_buildings(rvo3d_env *h, const double *buildings, const int32_t *counts, int32_t nb_max, void *stream);
+
 /* env_drone.drones_reset (env_drones.py:99) for the envs whose mask byte is
  * non-zero (env_mask NULL = every env). env_mask [E]. */
 int rvo3d_reset(rvo3d_env *h, const uint8_t *env_mask, void *stream);
