@@ -8,12 +8,8 @@
 namespace rvo3d {
 
 // ---- small state kernels -------------------------------------------------------
-// drone.reset (drone.py:270-291) for masked envs / drones.
-__global__ void reset_kernel(const Params P, const uint8_t* env_mask, const uint8_t* drone_mask) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= P.E * P.N) return;
-  if (env_mask && !env_mask[g / P.N]) return;
-  if (drone_mask && !drone_mask[g]) return;
+// drone.reset (drone.py:270-291) of drone g: every field a reset writes (shared with set_routes_kernel).
+__device__ __forceinline__ void reset_drone(const Params& P, int g) {
   double s[3];
   load_wp(P, g, 0, s);
   P.px()[g] = s[0]; P.py()[g] = s[1]; P.pz()[g] = s[2];
@@ -30,6 +26,14 @@ __global__ void reset_kernel(const Params P, const uint8_t* env_mask, const uint
   P.dvk_a()[g] = plain ? P.dv0_a()[g] : kDvInvalid;
   P.dvk_b()[g] = P.dv0_b()[g];
 }
+// ... for masked envs / drones.
+__global__ void reset_kernel(const Params P, const uint8_t* env_mask, const uint8_t* drone_mask) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= P.E * P.N) return;
+  if (env_mask && !env_mask[g / P.N]) return;
+  if (drone_mask && !drone_mask[g]) return;
+  reset_drone(P, g);
+}
 
 // cur / prev from the waypoint index (rvo3d_load_world; rvo3d_set_state with wp_idx)
 __global__ void wpcache_kernel(const Params P) {
@@ -45,11 +49,9 @@ __global__ void wpcache_kernel(const Params P) {
   store3(P.prev(0), P.prev(1), P.prev(2), g, v);
 }
 
-// rvo3d_load_world: dronestate of every drone's reset state (drone.py:254-263 after
+// rvo3d_load_world / rvo3d_set_routes: dronestate of a drone's reset state (drone.py:254-263 after
 // drone.reset, :270-291): des_vel towards waypoint 1 and the deviation from the first leg.
-__global__ void dv0_kernel(const Params P) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= P.E * P.N) return;
+__device__ __forceinline__ void dv0_drone(const Params& P, int g) {
   double p[3], cur[3], dv[3];
   load_wp(P, g, 0, p);
   load_wp(P, g, 1, cur);
@@ -58,6 +60,11 @@ __global__ void dv0_kernel(const Params P) {
   dv_encode(dv, a, b);
   P.dv0_a()[g] = a; P.dv0_b()[g] = b;
   P.dev0()[g] = deviation(p, cur, p);
+}
+__global__ void dv0_kernel(const Params P) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= P.E * P.N) return;
+  dv0_drone(P, g);
 }
 
 __global__ void des_vel_kernel(const Params P, double* out) {

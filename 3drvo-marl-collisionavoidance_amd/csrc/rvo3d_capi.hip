@@ -584,6 +584,78 @@ int rvo3d_set_env_buildings(rvo3d_env* h, const double* buildings, const int32_t
   RVO3D_API_END
 }
 
+int rvo3d_set_routes(rvo3d_env* h, const uint8_t* env_mask, const double* waypoints, const int32_t* n_points,
+                     void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!waypoints) return fail(RVO3D_ERR_INVALID, "waypoints is required");
+  if (!n_points) return fail(RVO3D_ERR_INVALID, "n_points is required");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  DeviceGuard dg;
+  if (int rc = dg.enter(h->cfg.device)) return rc;
+  const Params& P = h->P;
+  // one workgroup per env: it votes on the env's n_points before its first store
+  hipLaunchKernelGGL(rvo3d::set_routes_kernel, dim3((unsigned)P.E), dim3((unsigned)align_up((size_t)P.N, 64)), 0,
+                     static_cast<hipStream_t>(stream), P, env_mask, waypoints, n_points);
+  HIP_TRY(hipGetLastError());
+  h->g_valid = false;  // positions change: the stage-G words on file are stale (the des_vel on file is the reset state's)
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_get_routes(rvo3d_env* h, double* waypoints, int32_t* n_points, void* stream) {
+  RVO3D_API_BEGIN
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const Params& P = h->P;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t EN = (size_t)P.E * P.N;
+  if (waypoints) {
+    hipLaunchKernelGGL(rvo3d::get_routes_kernel, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, s, P, waypoints);
+    HIP_TRY(hipGetLastError());
+  }
+  if (n_points) HIP_TRY(hipMemcpyAsync(n_points, P.n_points(), EN * 4, hipMemcpyDeviceToDevice, s));
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_sample_routes(const rvo3d_route_sampler* cfg, int32_t num_envs, int32_t num_drones, int32_t max_points,
+                        uint32_t draw, const uint8_t* env_mask, double* waypoints, int32_t* n_points, int32_t* unplaced,
+                        void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  if (!cfg) return fail(RVO3D_ERR_INVALID, "cfg is required");
+  if (!waypoints) return fail(RVO3D_ERR_INVALID, "waypoints is required");
+  if (!n_points) return fail(RVO3D_ERR_INVALID, "n_points is required");
+  if (num_envs < 1 || num_drones < 1 || num_drones > rvo3d::kMaxThreads)
+    return fail(RVO3D_ERR_INVALID, "need num_envs >= 1 and 1 <= num_drones <= 512");
+  if (max_points < 2) return fail(RVO3D_ERR_INVALID, "need max_points >= 2");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(cfg->lo[k]) || !std::isfinite(cfg->hi[k]) || !(cfg->lo[k] < cfg->hi[k]))
+      return fail(RVO3D_ERR_INVALID, "lo / hi must be finite with lo < hi on every axis");
+  if (!(cfg->min_sep >= 0.0) || !(cfg->min_len >= 0.0)) return fail(RVO3D_ERR_INVALID, "min_sep and min_len must be >= 0");
+  if (cfg->max_tries < 1 || cfg->max_tries > 1024) return fail(RVO3D_ERR_INVALID, "max_tries must be 1..1024");
+  rvo3d::SampleRoutesArgs A;
+  for (int k = 0; k < 3; ++k) {
+    A.lo[k] = cfg->lo[k];
+    A.span[k] = cfg->hi[k] - cfg->lo[k];
+  }
+  A.sep2 = cfg->min_sep * cfg->min_sep; A.len2 = cfg->min_len * cfg->min_len;
+  A.max_tries = cfg->max_tries; A.N = num_drones; A.P = max_points;
+  A.draw = draw; A.k0 = (uint32_t)cfg->seed; A.k1 = (uint32_t)(cfg->seed >> 32);
+  A.env_offset = cfg->env_offset;
+  A.env_mask = env_mask; A.wp = waypoints; A.n_points = n_points; A.unplaced = unplaced;
+  // one workgroup per env, one lane per drone; LDS: one point per lane and the round's unplaced flags
+  const size_t T = align_up((size_t)num_drones, 64);
+  hipLaunchKernelGGL(rvo3d::sample_routes_kernel, dim3((unsigned)num_envs), dim3((unsigned)T), T * (3 * sizeof(double) + 1),
+                     static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
 int rvo3d_reset(rvo3d_env* h, const uint8_t* env_mask, void* stream) {
   RVO3D_API_BEGIN
   DeviceGuard dg;

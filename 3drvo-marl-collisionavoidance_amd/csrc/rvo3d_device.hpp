@@ -29,7 +29,8 @@
 // launch geometry, tables, the staged world; host only), rvo3d_math.hpp (arithmetic model, per-drone
 // pieces), rvo3d_lds.hpp (LDS views), rvo3d_pairs.hpp (pair pipeline), rvo3d_step.hpp (the step
 // kernel), rvo3d_aux_kernels.hpp (resets, tables, classical RVO selection), rvo3d_rollout_kernels.hpp (the
-// trainer's per-step glue: policy heads + sampling, episode bookkeeping), rvo3d_eval_kernels.hpp (the evaluator's:
+// trainer's per-step glue: policy heads + sampling, episode bookkeeping), rvo3d_route_kernels.hpp (routes re-drawn on
+// the device: per-env replacement, the Philox start / goal sampler), rvo3d_eval_kernels.hpp (the evaluator's:
 // action glue, episode records, per-env re-observation), rvo3d_mfma_tiles.hpp (what the three
 // matrix-core policy kernels share: operand types, fragment maps, bf16 pack / split, the split product), rvo3d_policy_mlp.hpp (config 3's MLP(256, 256)
 // policy step on the matrix cores), rvo3d_policy_mlp_x3.hpp (the same step with split-bf16 products: float32-class), rvo3d_policy_rnn_tiles.hpp (the
@@ -43,6 +44,7 @@
 #include "rvo3d_step.hpp"
 #include "rvo3d_aux_kernels.hpp"
 #include "rvo3d_rollout_kernels.hpp"
+#include "rvo3d_route_kernels.hpp"
 #include "rvo3d_eval_kernels.hpp"
 #include "rvo3d_mfma_tiles.hpp"
 #include "rvo3d_policy_mlp.hpp"

@@ -113,7 +113,8 @@ class StateView(C.Structure):
 
 
 # every symbol include/rvo3d.h declares (tests check the library exports them all)
-SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_buildings", "rvo3d_reset",
+SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_buildings", "rvo3d_set_routes",
+           "rvo3d_get_routes", "rvo3d_sample_routes", "rvo3d_reset",
            "rvo3d_reset_drones", "rvo3d_observe", "rvo3d_step", "rvo3d_step_autoreset",
            "rvo3d_step_policy", "rvo3d_step_ex", "rvo3d_policy_sample", "rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_pack",
            "rvo3d_policy_mlp_sample", "rvo3d_policy_mlp_x3_blob_bytes", "rvo3d_policy_mlp_x3_pack", "rvo3d_policy_mlp_x3_sample",
@@ -149,6 +150,9 @@ def lib():
     L.rvo3d_destroy.argtypes = [vp]
     L.rvo3d_load_world.argtypes = [vp] * 7
     L.rvo3d_set_env_buildings.argtypes = [vp, vp, vp, i32, vp]
+    L.rvo3d_set_routes.argtypes = [vp, vp, vp, vp, vp]
+    L.rvo3d_get_routes.argtypes = [vp, vp, vp, vp]
+    L.rvo3d_sample_routes.argtypes = [vp, i32, i32, i32, C.c_uint32, vp, vp, vp, vp, vp]
     L.rvo3d_reset.argtypes = [vp, vp, vp]
     L.rvo3d_reset_drones.argtypes = [vp, vp, vp]
     L.rvo3d_observe.argtypes = [vp, vp, vp, vp]

@@ -81,6 +81,7 @@ class BatchedDroneEnv:
         # it bumps its counter; writers that bypass it (.data, DLPack, raw pointers) call invalidate_outputs().
         self.reuse_obs = bool(reuse_obs)
         self._obs_ver = None
+        self._routes_set = False  # set_routes was called: the routes are part of the checkpoint
         self._args = _lib.StepArgs()
         self._args.acceler = float(acceler)
         # optional float64 copy of the reward, as the reference returns it (mdin.py:28)
@@ -124,6 +125,38 @@ class BatchedDroneEnv:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().rvo3d_set_env_buildings(self._h, hp(b), hp(c), nb_max, self._stream()),
                        "rvo3d_set_env_buildings")
+
+    def set_routes(self, waypoints, n_points=None, env_mask=None):
+        """New routes from the next call on (rvo3d_set_routes): waypoints [E, N, P, 3] float64, n_points [E, N] int32
+        (None: P everywhere), env_mask [E] bool / uint8 (None: every env) - device tensors, or numpy, which is uploaded.
+        A masked env ends up as an env of a freshly built BatchedDroneEnv with these routes, every drone in its reset
+        state; the other envs are not written.  An env with an n_points entry outside 2..P keeps what it had and raises
+        bit 4 of error_flags().  One launch on the current stream, no synchronisation.  obs / vo_count are not
+        touched: observe() afterwards."""
+        def dev(a, dt, shape, name):
+            if not torch.is_tensor(a):
+                a = torch.as_tensor(np.ascontiguousarray(a))
+            a = a.to(device=self.device, dtype=dt).contiguous()
+            if tuple(a.shape) != shape:
+                raise AssertionError(f"{name} must have shape {shape}")
+            return a
+        wp = dev(waypoints, torch.float64, (self.E, self.N, self.P, 3), "waypoints")
+        if n_points is None:
+            n_points = torch.full((self.E, self.N), self.P, dtype=torch.int32, device=self.device)
+        npts = dev(n_points, torch.int32, (self.E, self.N), "n_points")
+        m = None if env_mask is None else dev(env_mask, torch.uint8, (self.E,), "env_mask")
+        _lib.check(_lib.lib().rvo3d_set_routes(self._h, _ptr(m), _ptr(wp), _ptr(npts), self._stream()),
+                   "rvo3d_set_routes")
+        self._keep_routes = (wp, npts, m)  # the borrowed buffers live until the launch ran
+        self._routes_set = True
+
+    def routes(self):
+        """(waypoints [E, N, P, 3] float64 padded with each destination, n_points [E, N] int32): device copies of the
+        routes in force (rvo3d_get_routes)."""
+        wp = torch.empty((self.E, self.N, self.P, 3), dtype=torch.float64, device=self.device)
+        npts = torch.empty((self.E, self.N), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().rvo3d_get_routes(self._h, _ptr(wp), _ptr(npts), self._stream()), "rvo3d_get_routes")
+        return wp, npts
 
     def _actions(self, actions):
         a = actions
@@ -319,9 +352,13 @@ class BatchedDroneEnv:
     def state_dict(self):
         """The complete mutable state of every drone (drone.py:14-82) as CPU tensors, plus the
         shape it belongs to: enough to resume a rollout bit-exactly (the values the step keeps
-        on file between calls are derived data and are rebuilt by load_state_dict)."""
+        on file between calls are derived data and are rebuilt by load_state_dict).  Once set_routes has been
+        called the routes in force go along (`waypoints`, `n_points`); an untouched env's are its world's."""
         sd = {k: v.cpu() for k, v in self.get_state().items()}
         sd["shape"] = torch.tensor([self.E, self.N, self.P, self.nm])
+        if self._routes_set:
+            wp, npts = self.routes()
+            sd["waypoints"], sd["n_points"] = wp.cpu(), npts.cpu()
         return sd
 
     def load_state_dict(self, sd):
@@ -329,7 +366,9 @@ class BatchedDroneEnv:
         if shape != [self.E, self.N, self.P, self.nm]:
             raise ValueError(f"checkpoint is for E,N,P,nm = {shape}, this env has "
                              f"{[self.E, self.N, self.P, self.nm]}")
-        self.set_state(**{k: v for k, v in sd.items() if k != "shape"})
+        if "waypoints" in sd:  # the routes first: set_routes resets every drone, the state below follows them
+            self.set_routes(sd["waypoints"], sd["n_points"])
+        self.set_state(**{k: v for k, v in sd.items() if k not in ("shape", "waypoints", "n_points")})
 
     def error_flags(self) -> int:
         """Reads and clears the device error word (synchronises)."""
@@ -342,6 +381,8 @@ class BatchedDroneEnv:
         """The reference raises ValueError when an observation holds NaN/Inf
         (ir_gym.py:232-239); opt-in here because it synchronises."""
         f = self.error_flags()
+        if f & 4:  # RVO3D_FLAG_BAD_ROUTE
+            raise ValueError("set_routes: n_points entries must be in [2, max_points] (the env kept its routes)")
         if f & 2:  # RVO3D_FLAG_DOMAIN_ERROR: vel_obs3D.py:13 asin((r + mr) / norm), env_train=False
             raise ValueError("math domain error")
         if f & 1:

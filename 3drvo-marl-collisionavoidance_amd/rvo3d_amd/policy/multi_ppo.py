@@ -193,7 +193,8 @@ class multi_ppo:
                  max_update_num=None, mpi=False, figure_save_path=None, minibatch_size=None,
                  dist=None, sanitize_rewards=True, amp=False, reference_order=False, fused_rollout=True,
                  tune_gemms=True, tune_update=False, fused_mlp=True, graph_rollout=False, fused_mlp_fp32=False,
-                 fused_rnn_tiles=False, fused_gae=False, fused_rnn_fp32=False, **kwargs):
+                 fused_rnn_tiles=False, fused_gae=False, fused_rnn_fp32=False, route_sampler=None, redraw_every=1,
+                 **kwargs):
         np.random.seed(seed)
         self.env, self.ac, self.dist = env, ac_policy, dist
         # The agent order of the reference-order update comes from a generator of its own, seeded like
@@ -231,6 +232,13 @@ class multi_ppo:
         # buffer ignores it.  Opt-in: advantages / returns differ from gae_scan's by a few float32 ulps, so switching
         # it on changes the default results - flipping the default is a later decision
         self.fused_gae = bool(fused_gae)
+        # new routes at the epoch-end full reset (rvo3d_amd.routes.RouteSampler): in every epoch whose number is a
+        # multiple of redraw_every, route_sampler.redraw(env, draw=epoch) - two launches, nothing read back - takes the
+        # place of the reset of the drones the step has not reset (set_routes resets everybody).  None: nothing changes
+        if redraw_every < 1:
+            raise ValueError("redraw_every must be >= 1")
+        self.route_sampler, self.redraw_every = route_sampler, int(redraw_every)
+        self._epoch_no = 0  # epochs ended so far: the number of the epoch in flight
         # the fast paths' per-step launches replayed as HIP graphs from the second rollout on (see _collect_fused);
         # opt-in: measured at 64 x 4096, 0.158 ms per step with and 0.157-0.161 without - the gaps between the dependent
         # kernels of a graph are what they are between stream launches.  Across update(): the "mlp" graphs survive an
@@ -502,7 +510,7 @@ class multi_ppo:
                 # handled - one launch per step less than clearing it before every step; a timeout cannot occur, and
                 # the flag cannot be set, before since_full_reset exceeds max_ep_len or the epoch ends)
                 if epoch_ended or (since_full_reset > self.max_ep_len and int(ac["any_extra"].item()) != 0):
-                    env.reset_drones(ac["extra"])
+                    self._reset_extra(ac["extra"], epoch_ended)
                     env.observe(obs_out=buf.obs[t + 1], cnt_out=buf.cnt[t + 1])
                     ac["any_extra"].zero_()
         finally:
@@ -517,6 +525,17 @@ class multi_ppo:
             self._rnn0_dense = float((buf.cnt[:T] > 0).float().mean()) > 2e-3
         s = ac["sums"].sum(dim=0).tolist()
         return float(s[0] / max(s[1], 1.0))
+
+    def _reset_extra(self, extra, epoch_ended):
+        """The resets the fused step left to the trainer (timeouts; at the epoch's end everybody it did not reset) - or,
+        at the end of an epoch that re-draws (route_sampler), new routes for every env, which resets everybody."""
+        if not epoch_ended:
+            return self.env.reset_drones(extra)
+        epoch, self._epoch_no = self._epoch_no, self._epoch_no + 1
+        if self.route_sampler is not None and epoch % self.redraw_every == 0:
+            self.route_sampler.redraw(self.env, draw=epoch)
+        else:
+            self.env.reset_drones(extra)
 
     def collect(self, final_reset=True):
         """One epoch of steps_per_epoch env steps (multi_ppo.py:183-281), on the device.  The
@@ -571,7 +590,7 @@ class multi_ppo:
                 ret_sum += (self.ep_ret * ended).sum()
                 ret_n += ended.sum()
                 if epoch_ended or (extra is not None and bool(extra.any())):
-                    env.reset_drones(extra)
+                    self._reset_extra(extra, epoch_ended)
                     env.observe(obs_out=buf.obs[t + 1], cnt_out=buf.cnt[t + 1])
                 buf.finish_path(terminal)
                 self.ep_ret.masked_fill_(ended, 0.0)

@@ -43,11 +43,13 @@ enum { RVO3D_F32 = 0, RVO3D_F64 = 1, RVO3D_BF16 = 2 };
 enum {
   RVO3D_FLAG_NONFINITE_OBS = 1, /* an observation held NaN/Inf: the reference
                                    raises ValueError here (ir_gym.py:232-239) */
-  RVO3D_FLAG_DOMAIN_ERROR = 2   /* env_train = 0 only: a pair with r - 0.2 + mr < dis < r + mr
+  RVO3D_FLAG_DOMAIN_ERROR = 2,  /* env_train = 0 only: a pair with r - 0.2 + mr < dis < r + mr
                                    was approaching; the reference's get_alpha raises
                                    ValueError("math domain error") there (vel_obs3D.py:13,
                                    rvo_inter.py:144-165) and aborts the step; here the pair
                                    counts as "no velocity obstacle" and the step completes */
+  RVO3D_FLAG_BAD_ROUTE = 4      /* rvo3d_set_routes met an n_points entry outside 2..max_points:
+                                   that env kept the routes and the state it had */
 };
 
 typedef struct rvo3d_env rvo3d_env;
@@ -106,6 +108,57 @@ int rvo3d_load_world(rvo3d_env *h, const double *waypoints, const int32_t *n_poi
  * next call / rvo3d_destroy) and synchronises; step and observe still allocate nothing.  Every argument check runs
  * before the first HIP call; a refused call leaves the handle as it was. */
 int rvo3d_set_env_buildings(rvo3d_env *h, const double *buildings, const int32_t *counts, int32_t nb_max, void *stream);
+
+/* New routes for the envs whose mask byte is non-zero, from DEVICE memory: waypoints [E][N][P][3] (routes shorter than P
+ * padded with anything), n_points [E][N] (each 2..P), env_mask [E] (NULL = every env; the other two are required).  A
+ * masked env ends up exactly as an env of a handle freshly loaded (rvo3d_load_world) with these routes: the waypoint rows
+ * padded with the destination, n_points, the route lengths (drone.calculate_total_length, drone.py:409-429: the legs in
+ * order, a correctly rounded float64 sqrt per leg; a component is squared as x * x, the device's model of the reference's
+ * x ** 2, where rvo3d_load_world's host staging calls pow(x, 2): one ulp apart for about 1 leg in 5000), extra_len = 0,
+ * the reset state's des_vel and deviation, and every drone of the env in its reset state (drone.reset, drone.py:270-291).  Rows of unmasked envs are neither read nor is
+ * anything of those envs written; radius, priority, buildings (the shared list or per-env sets) stay.  An env with an
+ * n_points entry outside 2..P is left entirely as it was and raises RVO3D_FLAG_BAD_ROUTE in the device error word (one
+ * workgroup per env votes before its first store).  Needs a loaded world (RVO3D_ERR_STATE); a missing pointer is
+ * RVO3D_ERR_INVALID; every argument check runs before the first HIP call and a refused call leaves the handle as it was.
+ * Enqueues one launch: no synchronisation, no allocation.  The caller observes afterwards (rvo3d_observe). */
+int rvo3d_set_routes(rvo3d_env *h, const uint8_t *env_mask, const double *waypoints, const int32_t *n_points,
+                     void *stream);
+/* The handle's routes as DEVICE copies in the layout rvo3d_load_world takes: waypoints [E][N][P][3] with the padding as
+ * stored (the destination behind n_points), n_points [E][N].  Either pointer may be NULL. */
+int rvo3d_get_routes(rvo3d_env *h, double *waypoints, int32_t *n_points, void *stream);
+
+/* Start / goal pairs per env from a counter-based generator, written in rvo3d_set_routes' layout; the batched counterpart
+ * of uaisa_env/world/random_start_end.py (random pairs with a minimum separation).  No handle: cfg is a HOST struct, the
+ * other pointers DEVICE pointers of the current device, work enqueued on `stream`.  For the envs whose mask byte is
+ * non-zero (env_mask [E], NULL = every env): waypoints [E][N][P][3] receives the start, the end, and the end again in rows
+ * k >= 2; n_points [E][N] receives 2; unplaced [E] (nullable) the number of drones left unplaced, starts plus ends.  Rows
+ * of unmasked envs are not written.  The result is defined by these rules, to the last bit:
+ *   1. Candidate(kind, e, d, t), kind 0 = start, 1 = end: the Philox4x32-10 block of counter (c0 = low 32 bits of
+ *      env_offset + e, c1 = d, c2 = t + kind * 2^31, c3 = draw) under the key (seed low word, seed high word); of its
+ *      words x0..x2, u_k = ((double)x_k + 0.5) * 2^-32 and coord_k = rint((lo_k + u_k * (hi_k - lo_k)) * 100.0) / 100.0,
+ *      every operation rounded on its own in float64 (no FMA).
+ *   2. dist2(a, b) = (dx*dx + dy*dy) + dz*dz in float64, compared with min_sep*min_sep or min_len*min_len.
+ *   3. Placement(kind) per env; all drones start unplaced.  In round t = 0 .. max_tries-1 every unplaced drone d takes
+ *      c_d = Candidate(kind, e, d, t) and is accepted iff (a) dist2(c_d, p_j) >= min_sep^2 for every j placed in an
+ *      earlier round, (b) dist2(c_d, c_j) >= min_sep^2 for every j < d unplaced at the start of round t, accepted in this
+ *      round or not, and (c) - ends only - dist2(c_d, start_d) >= min_len^2.  Accepted drones count as placed from the
+ *      next round on; a drone still unplaced after the last round keeps its candidate of the last round.
+ *   4. Starts are placed first, then ends.
+ * env_offset: env e draws as env e + env_offset of a larger batch does (a shard's first env).  Ranges: lo / hi finite with
+ * lo < hi, min_sep >= 0, min_len >= 0, max_tries 1..1024, num_envs >= 1, num_drones 1..512, max_points >= 2
+ * (RVO3D_ERR_INVALID otherwise; every argument check runs before the first HIP call).  One workgroup per env; no
+ * synchronisation, no allocation, no atomics. */
+typedef struct rvo3d_route_sampler {
+  double lo[3], hi[3];   /* the box                                            */
+  double min_sep, min_len;
+  int32_t max_tries;
+  int32_t reserved;
+  uint64_t seed;
+  int64_t env_offset;
+} rvo3d_route_sampler;
+int rvo3d_sample_routes(const rvo3d_route_sampler *cfg, int32_t num_envs, int32_t num_drones, int32_t max_points,
+                        uint32_t draw, const uint8_t *env_mask, double *waypoints, int32_t *n_points, int32_t *unplaced,
+                        void *stream);
 
 /* env_drone.drones_reset (env_drones.py:99) for the envs whose mask byte is
  * non-zero (env_mask NULL = every env). env_mask [E]. */
