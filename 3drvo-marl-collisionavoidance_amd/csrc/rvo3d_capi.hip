@@ -621,22 +621,50 @@ int rvo3d_get_routes(rvo3d_env* h, double* waypoints, int32_t* n_points, void* s
   RVO3D_API_END
 }
 
-int rvo3d_sample_routes(const rvo3d_route_sampler* cfg, int32_t num_envs, int32_t num_drones, int32_t max_points,
-                        uint32_t draw, const uint8_t* env_mask, double* waypoints, int32_t* n_points, int32_t* unplaced,
-                        void* stream) {
-  RVO3D_API_BEGIN
-  // every argument check before the first HIP call
-  if (!cfg) return fail(RVO3D_ERR_INVALID, "cfg is required");
+}  // extern "C"
+
+namespace {
+
+// the argument checks of the two samplers and of the planner that do not concern a config struct
+int check_route_shape(const double* waypoints, const int32_t* n_points, int32_t num_envs, int32_t num_drones,
+                      int32_t max_points) {
   if (!waypoints) return fail(RVO3D_ERR_INVALID, "waypoints is required");
   if (!n_points) return fail(RVO3D_ERR_INVALID, "n_points is required");
   if (num_envs < 1 || num_drones < 1 || num_drones > rvo3d::kMaxThreads)
     return fail(RVO3D_ERR_INVALID, "need num_envs >= 1 and 1 <= num_drones <= 512");
   if (max_points < 2) return fail(RVO3D_ERR_INVALID, "need max_points >= 2");
+  return RVO3D_OK;
+}
+
+rvo3d::CityArgs city_args(const rvo3d_city& c) {
+  rvo3d::CityArgs a;
+  a.bld = c.nb_max > 0 ? c.buildings : nullptr;
+  a.counts = c.counts; a.stride = c.env_stride; a.nb_max = c.nb_max;
+  a.clear_xy = c.clear_xy; a.clear_z = c.clear_z; a.pad = c.pad;
+  return a;
+}
+
+// LDS bytes of an env's staged building records
+size_t city_lds_bytes(const rvo3d_city& c) {
+  return (size_t)(c.nb_max < rvo3d::kCityLdsCap ? c.nb_max : rvo3d::kCityLdsCap) * 4 * sizeof(double);
+}
+
+// rvo3d_sample_routes and rvo3d_sample_routes_city (with_city): one set of checks, one launch
+int sample_routes(const rvo3d_route_sampler* cfg, bool with_city, const rvo3d_city* city, int32_t num_envs,
+                  int32_t num_drones, int32_t max_points, uint32_t draw, const uint8_t* env_mask, double* waypoints,
+                  int32_t* n_points, int32_t* unplaced, void* stream) {
+  // every argument check before the first HIP call
+  if (!cfg) return fail(RVO3D_ERR_INVALID, "cfg is required");
+  if (int rc = check_route_shape(waypoints, n_points, num_envs, num_drones, max_points)) return rc;
   for (int k = 0; k < 3; ++k)
     if (!std::isfinite(cfg->lo[k]) || !std::isfinite(cfg->hi[k]) || !(cfg->lo[k] < cfg->hi[k]))
       return fail(RVO3D_ERR_INVALID, "lo / hi must be finite with lo < hi on every axis");
   if (!(cfg->min_sep >= 0.0) || !(cfg->min_len >= 0.0)) return fail(RVO3D_ERR_INVALID, "min_sep and min_len must be >= 0");
   if (cfg->max_tries < 1 || cfg->max_tries > 1024) return fail(RVO3D_ERR_INVALID, "max_tries must be 1..1024");
+  if (with_city) {
+    std::string err;
+    if (int rc = rvo3d::check_city(city, err)) return fail(rc, err);
+  }
   rvo3d::SampleRoutesArgs A;
   for (int k = 0; k < 3; ++k) {
     A.lo[k] = cfg->lo[k];
@@ -649,8 +677,58 @@ int rvo3d_sample_routes(const rvo3d_route_sampler* cfg, int32_t num_envs, int32_
   A.env_mask = env_mask; A.wp = waypoints; A.n_points = n_points; A.unplaced = unplaced;
   // one workgroup per env, one lane per drone; LDS: one point per lane and the round's unplaced flags
   const size_t T = align_up((size_t)num_drones, 64);
-  hipLaunchKernelGGL(rvo3d::sample_routes_kernel, dim3((unsigned)num_envs), dim3((unsigned)T), T * (3 * sizeof(double) + 1),
-                     static_cast<hipStream_t>(stream), A);
+  const size_t lds = T * (3 * sizeof(double) + 1);
+  if (with_city)  // ... and the env's building records between the two
+    hipLaunchKernelGGL(rvo3d::sample_routes_city_kernel, dim3((unsigned)num_envs), dim3((unsigned)T),
+                       lds + city_lds_bytes(*city), static_cast<hipStream_t>(stream), A, city_args(*city));
+  else
+    hipLaunchKernelGGL(rvo3d::sample_routes_kernel, dim3((unsigned)num_envs), dim3((unsigned)T), lds,
+                       static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rvo3d_sample_routes(const rvo3d_route_sampler* cfg, int32_t num_envs, int32_t num_drones, int32_t max_points,
+                        uint32_t draw, const uint8_t* env_mask, double* waypoints, int32_t* n_points, int32_t* unplaced,
+                        void* stream) {
+  RVO3D_API_BEGIN
+  return sample_routes(cfg, false, nullptr, num_envs, num_drones, max_points, draw, env_mask, waypoints, n_points,
+                       unplaced, stream);
+  RVO3D_API_END
+}
+
+int rvo3d_sample_routes_city(const rvo3d_route_sampler* cfg, const rvo3d_city* city, int32_t num_envs, int32_t num_drones,
+                             int32_t max_points, uint32_t draw, const uint8_t* env_mask, double* waypoints,
+                             int32_t* n_points, int32_t* unplaced, void* stream) {
+  RVO3D_API_BEGIN
+  return sample_routes(cfg, true, city, num_envs, num_drones, max_points, draw, env_mask, waypoints, n_points, unplaced,
+                       stream);
+  RVO3D_API_END
+}
+
+int rvo3d_plan_routes(const rvo3d_city* city, int32_t num_envs, int32_t num_drones, int32_t max_points,
+                      const uint8_t* env_mask, double* waypoints, int32_t* n_points, int32_t* blocked,
+                      uint8_t* blocked_mask, void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  std::string err;
+  if (int rc = rvo3d::check_city(city, err)) return fail(rc, err);
+  if (int rc = check_route_shape(waypoints, n_points, num_envs, num_drones, max_points)) return rc;
+  rvo3d::PlanRoutesArgs A;
+  A.city = city_args(*city);
+  A.N = num_drones; A.P = max_points;
+  A.env_mask = env_mask; A.wp = waypoints; A.n_points = n_points; A.blocked = blocked; A.blocked_mask = blocked_mask;
+  // one workgroup per env, one lane per drone; LDS: the env's building records
+  const dim3 grid((unsigned)num_envs), block((unsigned)align_up((size_t)num_drones, 64));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (max_points <= rvo3d::kPlanPrivatePoints)
+    hipLaunchKernelGGL(rvo3d::plan_routes_kernel<true>, grid, block, city_lds_bytes(*city), s, A);
+  else
+    hipLaunchKernelGGL(rvo3d::plan_routes_kernel<false>, grid, block, city_lds_bytes(*city), s, A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END

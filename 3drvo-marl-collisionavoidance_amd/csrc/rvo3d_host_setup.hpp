@@ -313,6 +313,36 @@ inline int check_env_buildings(int E, const double* buildings, const int32_t* co
   return RVO3D_OK;
 }
 
+// The checks rvo3d_sample_routes_city and rvo3d_plan_routes make of their rvo3d_city (its pointers are device
+// pointers: what they point at is the kernels' to bound).
+inline int check_city(const rvo3d_city* c, std::string& err) {
+  if (!c) {
+    err = "city is required";
+    return RVO3D_ERR_INVALID;
+  }
+  if (!std::isfinite(c->clear_xy) || !std::isfinite(c->clear_z) || !(c->clear_xy >= 0.0) || !(c->clear_z >= 0.0)) {
+    err = "clear_xy and clear_z must be finite and >= 0";
+    return RVO3D_ERR_INVALID;
+  }
+  if (!std::isfinite(c->pad) || !(c->pad > 0.0)) {
+    err = "pad must be finite and > 0";
+    return RVO3D_ERR_INVALID;
+  }
+  if (c->nb_max < 0 || c->nb_max > kMaxBuildings) {
+    err = "nb_max must be in [0, 65535)";
+    return RVO3D_ERR_INVALID;
+  }
+  if (c->env_stride != 0 && c->env_stride != (int64_t)c->nb_max * 4) {
+    err = "env_stride must be 0 (one shared list) or nb_max * 4 (a set per env)";
+    return RVO3D_ERR_INVALID;
+  }
+  if (c->nb_max > 0 && !c->buildings) {
+    err = "buildings is required when nb_max > 0";
+    return RVO3D_ERR_INVALID;
+  }
+  return RVO3D_OK;
+}
+
 // Grid dimensions of the per-env lists: the shared path's (building_grid_dims) when E grids of them fit the
 // budget, else the cell size grows until they do - down to one cell per env, which is the floor (beyond
 // budget / 32 envs even that exceeds the budget).  Results do not depend on the dimensions: the lists are

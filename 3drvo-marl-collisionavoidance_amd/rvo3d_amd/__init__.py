@@ -13,8 +13,8 @@ from ._lib import build_hip, lib, lib_path, RVO3DError  # noqa: F401
 from .batched_env import BatchedDroneEnv  # noqa: F401
 from .worlds import (World, crossing_world, load_world_dir, stack_worlds, synthetic_world,  # noqa: F401
                      synthetic_actions)
-from .routes import RouteSampler  # noqa: F401
+from .routes import CityRoutePlanner, RouteSampler  # noqa: F401
 from . import sharding  # noqa: F401
 
-__all__ = ["BatchedDroneEnv", "RouteSampler", "World", "crossing_world", "load_world_dir", "stack_worlds", "synthetic_world",
+__all__ = ["BatchedDroneEnv", "CityRoutePlanner", "RouteSampler", "World", "crossing_world", "load_world_dir", "stack_worlds", "synthetic_world",
            "synthetic_actions", "build_hip", "lib", "lib_path", "RVO3DError"]

@@ -114,7 +114,7 @@ class StateView(C.Structure):
 
 # every symbol include/rvo3d.h declares (tests check the library exports them all)
 SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_buildings", "rvo3d_set_routes",
-           "rvo3d_get_routes", "rvo3d_sample_routes", "rvo3d_reset",
+           "rvo3d_get_routes", "rvo3d_sample_routes", "rvo3d_sample_routes_city", "rvo3d_plan_routes", "rvo3d_reset",
            "rvo3d_reset_drones", "rvo3d_observe", "rvo3d_step", "rvo3d_step_autoreset",
            "rvo3d_step_policy", "rvo3d_step_ex", "rvo3d_policy_sample", "rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_pack",
            "rvo3d_policy_mlp_sample", "rvo3d_policy_mlp_x3_blob_bytes", "rvo3d_policy_mlp_x3_pack", "rvo3d_policy_mlp_x3_sample",
@@ -153,6 +153,8 @@ def lib():
     L.rvo3d_set_routes.argtypes = [vp, vp, vp, vp, vp]
     L.rvo3d_get_routes.argtypes = [vp, vp, vp, vp]
     L.rvo3d_sample_routes.argtypes = [vp, i32, i32, i32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.rvo3d_sample_routes_city.argtypes = [vp, vp, i32, i32, i32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.rvo3d_plan_routes.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.rvo3d_reset.argtypes = [vp, vp, vp]
     L.rvo3d_reset_drones.argtypes = [vp, vp, vp]
     L.rvo3d_observe.argtypes = [vp, vp, vp, vp]

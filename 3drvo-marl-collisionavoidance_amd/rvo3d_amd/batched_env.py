@@ -55,6 +55,8 @@ class BatchedDroneEnv:
         h = C.c_void_p()
         _lib.check(L.rvo3d_create(C.byref(cfg), C.byref(h)), "rvo3d_create")
         self._h = h
+        self._env_bld = None  # the last set_env_buildings: (buildings, counts) host arrays, None: the world's shared list
+        self._dev_bld = None  # device_buildings()' cache
         wp = np.ascontiguousarray(world.waypoints, dtype=np.float64)
         npts = np.ascontiguousarray(world.n_points, dtype=np.int32)
         bld = np.zeros((0, 4)) if per_env else np.ascontiguousarray(world.buildings, dtype=np.float64)
@@ -125,6 +127,22 @@ class BatchedDroneEnv:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().rvo3d_set_env_buildings(self._h, hp(b), hp(c), nb_max, self._stream()),
                        "rvo3d_set_env_buildings")
+        self._env_bld = None if b is None or nb_max == 0 else (b.copy(), None if c is None else c.copy())
+        self._dev_bld = None
+
+    def device_buildings(self):
+        """What the env collides with now, as device tensors: (buildings [1, nb, 4] - the world's shared list - or
+        [E, nb_max, 4] - the sets of the last set_env_buildings - float64, counts [E] int32 or None).  Built on first
+        use and kept until the next set_env_buildings; CityRoutePlanner.redraw reads the city from here."""
+        if self._dev_bld is None:
+            if self._env_bld is not None:
+                b, c = self._env_bld
+            else:  # the shared list rvo3d_load_world took (none for a world of per-env sets)
+                b = np.zeros((0, 4)) if self.world.per_env_buildings else np.asarray(self.world.buildings, np.float64)
+                b, c = b.reshape(1, -1, 4), None
+            self._dev_bld = (torch.from_numpy(np.ascontiguousarray(b)).to(self.device),
+                             None if c is None else torch.from_numpy(c).to(self.device))
+        return self._dev_bld
 
     def set_routes(self, waypoints, n_points=None, env_mask=None):
         """New routes from the next call on (rvo3d_set_routes): waypoints [E, N, P, 3] float64, n_points [E, N] int32

@@ -35,6 +35,20 @@ class World:
         n = self.buildings.shape[1] if self.building_counts is None else int(self.building_counts[e])
         return self.buildings[e, :n]
 
+    def with_max_points(self, P: int) -> "World":
+        """The same world with the waypoint rows padded with each destination up to P rows: room for the detours a
+        CityRoutePlanner inserts.  P below the rows in use is a ValueError."""
+        wp = np.asarray(self.waypoints, dtype=np.float64)
+        E, N, p = wp.shape[:3]
+        if P < int(np.max(self.n_points, initial=2)):
+            raise ValueError("with_max_points: P is below the longest route")
+        last = np.take_along_axis(wp, (np.asarray(self.n_points).astype(np.int64) - 1)[:, :, None, None], axis=2)
+        out = np.broadcast_to(last, (E, N, P, 3)).copy()
+        k = min(p, P)
+        used = np.arange(k)[None, None, :, None] < np.asarray(self.n_points)[:, :, None, None]
+        out[:, :, :k] = np.where(used, wp[:, :, :k], out[:, :, :k])
+        return World(out, np.array(self.n_points, dtype=np.int32), self.map_size, self.buildings, self.building_counts)
+
     def select(self, envs) -> "World":
         """The world of the listed envs (indices, a slice or a mask over E); a shared list stays shared."""
         per = self.per_env_buildings

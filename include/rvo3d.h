@@ -160,6 +160,68 @@ int rvo3d_sample_routes(const rvo3d_route_sampler *cfg, int32_t num_envs, int32_
                         uint32_t draw, const uint8_t *env_mask, double *waypoints, int32_t *n_points, int32_t *unplaced,
                         void *stream);
 
+/* The city a route re-draw goes round: a HOST struct whose pointers are DEVICE pointers.  A building is
+ * b = (x_b, y_b, h_b, r_b), four doubles.  Env e sees buildings + e * env_stride as [nb_max][4] doubles - env_stride = 0:
+ * one list shared by every env, env_stride = nb_max * 4: a set per env - and of those the records 0 .. counts[e]-1
+ * (counts == NULL: all nb_max; an entry outside 0 .. nb_max is clamped into that range on the device).  nb_max == 0
+ * means no buildings; nb_max < 65535 as for rvo3d_set_env_buildings.  Definitions both calls below share, every value a
+ * float64 and every operation rounded on its own (no FMA):
+ *   R_b = r_b + clear_xy, top_b = h_b + clear_z, r2(v) = rint(v * 100.0) / 100.0,
+ *   max(x, y) = x > y ? x : y, min(x, y) = x < y ? x : y,
+ *   inside(p, b) iff ((p_x - x_b)*(p_x - x_b) + (p_y - y_b)*(p_y - y_b)) < R_b*R_b and p_z <= top_b.
+ * Checked by both calls before their first HIP call (RVO3D_ERR_INVALID): clear_xy, clear_z finite and >= 0, pad finite
+ * and > 0, nb_max in [0, 65535), env_stride 0 or nb_max * 4, buildings non-NULL when nb_max > 0. */
+typedef struct rvo3d_city {
+  const double *buildings;
+  const int32_t *counts;
+  int64_t env_stride;      /* doubles per env */
+  int32_t nb_max;
+  double clear_xy, clear_z; /* the clearance kept from a building's wall and roof */
+  double pad;              /* rvo3d_plan_routes: how far outside the clearance cylinder a detour point lies */
+} rvo3d_city;
+
+/* rvo3d_sample_routes with one more acceptance rule.  Rules 1, 2, 3 and 4 hold unchanged; rule 3 gains
+ *   (d) c_d is accepted only if inside(c_d, b) is false for every building b of its env - starts and ends alike.
+ * A candidate refused by (d) still counts as c_j in (b) for the drones behind it, so the rounds stay a parallel vote.
+ * With no buildings the outputs equal rvo3d_sample_routes' bit for bit.  pad is checked and not used.  Everything else -
+ * arguments, ranges, masking, one workgroup per env, no synchronisation, no allocation, no atomics - as there. */
+int rvo3d_sample_routes_city(const rvo3d_route_sampler *cfg, const rvo3d_city *city, int32_t num_envs, int32_t num_drones,
+                             int32_t max_points, uint32_t draw, const uint8_t *env_mask, double *waypoints,
+                             int32_t *n_points, int32_t *unplaced, void *stream);
+
+/* The detour planner: routes that go round the buildings, in place.  DEVICE pointers: waypoints [E][N][P][3] holds on
+ * entry the start in row 0 and the goal in row 1 (the samplers' layout; the other rows are not read) and on return each
+ * drone's points with the goal in every row behind them; n_points [E][N] receives the number of points; blocked [E]
+ * (nullable) the number of drones of the env whose route FAILED, blocked_mask [E][N] (nullable) one byte per drone, 1 for
+ * failed.  env_mask [E] (NULL = every env): nothing of an unmasked env is read or written.  The batched counterpart of
+ * the reference's offline Theta* run (uaisa_env/world/theta_star_3D.py); the result is defined by these rules, to the
+ * last bit.
+ *   Blocks(A, B, b) - is the leg A -> B blocked by b, and at which (t0, tc):
+ *     dx = B_x - A_x, dy, dz likewise; a = dx*dx + dy*dy; fx = A_x - x_b, fy = A_y - y_b; c = (fx*fx + fy*fy) - R_b*R_b.
+ *     a == 0: blocked iff c < 0 and min(A_z, B_z) <= top_b; t0 = tc = 0.
+ *     a != 0: bq = fx*dx + fy*dy; disc = bq*bq - a*c; not blocked unless disc > 0; s = sqrt(disc), correctly rounded;
+ *       t0 = (-bq - s) / a, t1 = (-bq + s) / a; not blocked if t1 <= 0 or t0 >= 1; t0 = max(t0, 0), t1 = min(t1, 1);
+ *       z0 = A_z + t0*dz, z1 = A_z + t1*dz; blocked iff min(z0, z1) <= top_b; tc = min(max(-bq / a, 0), 1).
+ *   FirstBlocker(A, B): the blocking building with the smallest t0, the lowest index among equals (a scan in index order
+ *     with a strict <).
+ *   Plan, per drone: pts = [start, goal], i = 0; while i < len(pts) - 1, with A = pts[i] and B = pts[i+1]:
+ *     no blocker: i += 1.  Otherwise, b being the first blocker: the drone FAILS if len(pts) == P or a == 0; else
+ *     l2 = sqrt(a); q = (A_x + tc*dx, A_y + tc*dy); n = q - (x_b, y_b); nl = sqrt(n_x*n_x + n_y*n_y);
+ *     if nl < 1e-6: n = (-dy, dx), nl = l2 (the leg runs through the axis: its left normal);
+ *     D = (r_b + clear_xy) + pad; W = (r2(x_b + (n_x/nl)*D), r2(y_b + (n_y/nl)*D), r2(A_z + tc*dz));
+ *     the drone FAILS if W equals A or B in all three coordinates; else W is inserted behind pts[i] and i stays: the
+ *     shortened leg is tested again.
+ * A failed drone keeps the points it has: a valid route that still crosses a clearance cylinder.  With no buildings, or
+ * with P == 2, no point is ever inserted.  Detours go round a building, never over it.
+ * Ranges: the city's (above), num_envs >= 1, num_drones 1..512, max_points >= 2, waypoints and n_points non-NULL
+ * (RVO3D_ERR_INVALID otherwise; every argument check runs before the first HIP call).  One workgroup per env, one lane
+ * per drone; an env's building records are staged in LDS when there are at most 256 of them and read from global memory
+ * otherwise; a drone's points are kept in private memory up to max_points = 16 and in its rows of `waypoints` beyond.
+ * One launch: no synchronisation, no allocation, no atomics. */
+int rvo3d_plan_routes(const rvo3d_city *city, int32_t num_envs, int32_t num_drones, int32_t max_points,
+                      const uint8_t *env_mask, double *waypoints, int32_t *n_points, int32_t *blocked,
+                      uint8_t *blocked_mask, void *stream);
+
 /* env_drone.drones_reset (env_drones.py:99) for the envs whose mask byte is
  * non-zero (env_mask NULL = every env). env_mask [E]. */
 int rvo3d_reset(rvo3d_env *h, const uint8_t *env_mask, void *stream);
