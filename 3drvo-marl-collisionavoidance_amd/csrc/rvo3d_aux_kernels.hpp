@@ -35,6 +35,15 @@ __global__ void reset_kernel(const Params P, const uint8_t* env_mask, const uint
   reset_drone(P, g);
 }
 
+// ... for the envs whose drone count changes (rvo3d_set_drone_counts): as a freshly loaded handle's, extra_len included.
+__global__ void reset_fresh_kernel(const Params P, const uint8_t* env_mask) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= P.E * P.N) return;
+  if (!env_mask[g / P.N]) return;
+  reset_drone(P, g);
+  P.extra_len()[g] = 0.0;
+}
+
 // cur / prev from the waypoint index (rvo3d_load_world; rvo3d_set_state with wp_idx)
 __global__ void wpcache_kernel(const Params P) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,14 +76,27 @@ __global__ void dv0_kernel(const Params P) {
   dv0_drone(P, g);
 }
 
-__global__ void des_vel_kernel(const Params P, double* out) {
+// The live drones of env e of a handle with drone counts (rvo3d_set_drone_counts): what the *_counted kernels read.
+__device__ __forceinline__ int live_drones(const Params& P, int e) { return P.cold().counts[e]; }
+
+template <bool CNT>
+__device__ __forceinline__ void des_vel_body(const Params P, double* out) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= P.E * P.N) return;
+  if (CNT) {  // a ghost's row is zero
+    const int e = g / P.N;
+    if (g - e * P.N >= live_drones(P, e)) {
+      out[3 * (size_t)g] = 0.0; out[3 * (size_t)g + 1] = 0.0; out[3 * (size_t)g + 2] = 0.0;
+      return;
+    }
+  }
   double p[3] = {P.px()[g], P.py()[g], P.pz()[g]}, cur[3], dv[3];
   load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
   des_vel(P, p, cur, dv);
   out[3 * (size_t)g] = dv[0]; out[3 * (size_t)g + 1] = dv[1]; out[3 * (size_t)g + 2] = dv[2];
 }
+__global__ void des_vel_kernel(const Params P, double* out) { des_vel_body<false>(P, out); }
+__global__ void des_vel_counted_kernel(const Params P, double* out) { des_vel_body<true>(P, out); }
 
 // ---- classical RVO velocity selection -----------------------------------
 // uaisa_env/vel_obs/reciprocal_vel_obs.py:19-166 as intended (the class cannot run: list
@@ -96,13 +118,21 @@ __device__ __forceinline__ double arange_at(double lo, int k) {  // numpy fills 
   return k == 0 ? lo : (k == 1 ? next : lo + k * (next - lo));
 }
 
-__global__ void __launch_bounds__(512) rvo_vel_kernel(const Params P, const RvoVelArgs A, double* out) {
+// CNT (rvo_vel_counted_kernel): the env's drones are the first live_drones(P, e) of its P.N rows; the ghosts are invisible
+// to them and their own rows are zero.
+template <bool CNT>
+__device__ __forceinline__ void rvo_vel_body(const Params P, const RvoVelArgs A, double* out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int N = P.N, d = threadIdx.x, e = blockIdx.x;
+  const int d = threadIdx.x, e = blockIdx.x;
+  const int N = CNT ? live_drones(P, e) : P.N;  // the drones the env has
   const int T = blockDim.x;
   double* const lx = reinterpret_cast<double*>(smem);  // x y z vx vy vz r prio, [T] each
   const bool active = d < N;
-  const int g = active ? e * N + d : e * N;
+  const int g = active ? e * P.N + d : e * P.N;
+  if (CNT && !active && d < P.N) {
+    double* o = out + 3 * ((size_t)e * P.N + d);
+    o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
+  }
   Drone S;
   S.x = P.px()[g]; S.y = P.py()[g]; S.z = P.pz()[g];
   S.vx = P.vx()[g]; S.vy = P.vy()[g]; S.vz = P.vz()[g];
@@ -228,6 +258,12 @@ __global__ void __launch_bounds__(512) rvo_vel_kernel(const Params P, const RvoV
   if (have_out) { o[0] = so[0]; o[1] = so[1]; o[2] = so[2]; }
   else if (have_in) { o[0] = si[0]; o[1] = si[1]; o[2] = si[2]; }
   else { o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; }
+}
+__global__ void __launch_bounds__(512) rvo_vel_kernel(const Params P, const RvoVelArgs A, double* out) {
+  rvo_vel_body<false>(P, A, out);
+}
+__global__ void __launch_bounds__(512) rvo_vel_counted_kernel(const Params P, const RvoVelArgs A, double* out) {
+  rvo_vel_body<true>(P, A, out);
 }
 
 // AoS <-> SoA copies for get_state / set_state

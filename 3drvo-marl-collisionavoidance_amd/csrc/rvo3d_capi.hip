@@ -68,6 +68,15 @@ struct rvo3d_env {
   // stays the shared list's description; the device copy of Cold is whichever of the two is in force.
   void* env_bld = nullptr;
   double rmax = 0.0;  // largest drone radius of the loaded world: the reach of the building lists
+  rvo3d::Cold live;   // host mirror of the device copy of Cold (the shared list's or the per-env sets', with the counts)
+  // per-env drone counts (rvo3d_set_drone_counts): attached while `counted`; the device array is allocated by the first
+  // attaching call and kept until rvo3d_destroy
+  bool counted = false;
+  int32_t* counts_dev = nullptr;
+  std::vector<int32_t> counts;  // host copy of the counts in force
+  rvo3d::Geometry cgeo{};       // launch geometry of the counted step
+  bool ctwo_phase = false;      // Cold::cnt_two_phase while attached
+  int lds_pad = 0;              // diagnostics build only: the extra LDS bytes of every step launch (0 in the product)
 };
 
 namespace {
@@ -104,6 +113,7 @@ int carve(rvo3d_env* h) {
     off += align_up(x.bytes, 256);
   }
   HIP_TRY(hipMemcpy((void*)P.cold_, &C, sizeof C, hipMemcpyHostToDevice));  // complete by now
+  h->live = C;
   return RVO3D_OK;
 }
 
@@ -144,8 +154,28 @@ void launch_train(rvo3d_env* h, const Params& P, hipStream_t s) {
   else launch_inst<MODE, NW, NFIX, false, PAD>(h, P, s);
 }
 
+// a handle with drone counts: the counted twin of the padded compile-time ring pick_counted_kernel names
+template <int MODE, int NW, int NFIX>
+void launch_counted(rvo3d_env* h, const Params& P, hipStream_t s) {
+  const dim3 grid(h->cgeo.blocks), block(h->cgeo.threads);
+  if (P.env_train) hipLaunchKernelGGL((rvo3d::env_kernel_counted<MODE, NW, NFIX, true>), grid, block, h->cgeo.lds, s, P);
+  else hipLaunchKernelGGL((rvo3d::env_kernel_counted<MODE, NW, NFIX, false>), grid, block, h->cgeo.lds, s, P);
+}
+
 template <int MODE, int NW>
 int launch_nw(rvo3d_env* h, const Params& P, hipStream_t s) {
+  if (h->counted) {
+    if constexpr (NW == 1) {
+      if (rvo3d::pick_counted_kernel(P).nfix == 32) launch_counted<MODE, 1, 32>(h, P, s);
+      else launch_counted<MODE, 1, 64>(h, P, s);
+    } else if constexpr (NW == 2 || NW == 3 || NW == 4) {
+      launch_counted<MODE, NW, 64 * NW>(h, P, s);
+    } else {
+      return fail(RVO3D_ERR_INVALID, "drone counts need num_drones <= 256");
+    }
+    HIP_TRY(hipGetLastError());
+    return RVO3D_OK;
+  }
   const Pick k = pick_kernel(P);
   if constexpr (NW == 1) {
     if (k.nfix == 64) { if (k.pad) launch_train<MODE, 1, 64, true>(h, P, s); else launch_train<MODE, 1, 64, false>(h, P, s); }
@@ -452,6 +482,7 @@ int rvo3d_create(const rvo3d_config* cfg, rvo3d_env** out) {
   if (const char* pad = std::getenv("RVO3D_LDS_PAD")) lds_pad = std::atoi(pad);  // diagnostics build only: cap occupancy
 #endif
   std::string err;
+  h->lds_pad = lds_pad;
   if (int rc = rvo3d::plan_env(cfg, lds_pad, P, h->cold, h->geo, err)) return fail(rc, err);
 #ifdef RVO3D_DIAG
   if (const char* ab = std::getenv("RVO3D_ABLATE")) P.ablate = std::atoi(ab);  // diagnostics build only
@@ -477,6 +508,7 @@ int rvo3d_destroy(rvo3d_env* h) {
   (void)dg.enter(h->cfg.device);
   (void)hipDeviceSynchronize();
   if (h->env_bld) (void)hipFree(h->env_bld);
+  if (h->counts_dev) (void)hipFree(h->counts_dev);
   if (h->arena) (void)hipFree(h->arena);
   delete h;
   return RVO3D_OK;
@@ -499,8 +531,9 @@ int rvo3d_load_world(rvo3d_env* h, const double* waypoints, const int32_t* n_poi
   rvo3d::StagedWorld w;
   std::string err;
   if (int rc2 = rvo3d::stage_world(h->P, waypoints, n_points, radius, priority, w, err)) return fail(rc2, err);
-  // a new world drops per-env building sets: the shared list is in force again (their allocation goes at the end)
-  if (h->env_bld) HIP_TRY(hipMemcpyAsync((void*)P.cold_, &C, sizeof C, hipMemcpyHostToDevice, s));
+  // a new world drops per-env building sets and drone counts: the shared list and full envs are in force again (the
+  // sets' allocation goes at the end)
+  if (h->env_bld || h->counted) HIP_TRY(hipMemcpyAsync((void*)P.cold_, &C, sizeof C, hipMemcpyHostToDevice, s));
   // [P][3] rows of EN doubles into arrays of stride S
   HIP_TRY(hipMemcpy2DAsync((void*)P.wp(0, 0), (size_t)P.S * 8, w.wp.data(), EN * 8, EN * 8,
                            (size_t)P.P * 3, hipMemcpyHostToDevice, s));
@@ -529,6 +562,9 @@ int rvo3d_load_world(rvo3d_env* h, const double* waypoints, const int32_t* n_poi
     (void)hipFree(h->env_bld);
     h->env_bld = nullptr;
   }
+  h->live = C;
+  h->counted = false;
+  h->counts.clear();
   h->rmax = rvo3d::largest_radius(w.rad);
   h->world_loaded = true;
   h->dv_valid = true;  // reset_kernel filed the des_vel of every start state
@@ -558,6 +594,7 @@ int rvo3d_set_env_buildings(rvo3d_env* h, const double* buildings, const int32_t
     C.bld_stride = (uint32_t)nb_max * 4u;
     C.bgrid_stride = (uint32_t)((size_t)C.bgx * C.bgy * (rvo3d::kBgridK + 1));
   }
+  C.counts = h->live.counts; C.cnt_two_phase = h->live.cnt_two_phase;  // drone counts stay as they are
   DeviceGuard dg;
   if (int rc = dg.enter(h->cfg.device)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -580,6 +617,85 @@ int rvo3d_set_env_buildings(rvo3d_env* h, const double* buildings, const int32_t
   }
   if (h->env_bld) (void)hipFree(h->env_bld);
   h->env_bld = buf;
+  h->live = C;
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_set_drone_counts(rvo3d_env* h, const int32_t* counts, void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check, and all of the host's work, before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  const Params& P = h->P;
+  bool detach = false;
+  std::string err;
+  if (int rc = rvo3d::check_drone_counts(P.E, P.N, counts, detach, err)) return fail(rc, err);
+  if (detach && !h->counted) return RVO3D_OK;  // full envs already
+  rvo3d::Geometry cgeo{};
+  bool two_phase = false;
+  if (!detach)
+    if (int rc = rvo3d::counted_geometry(h->lds_pad, P, h->geo, cgeo, two_phase, err)) return fail(rc, err);
+  // the envs whose count changes (no counts: every env has N drones)
+  std::vector<int32_t> now(counts ? counts : nullptr, counts ? counts + P.E : nullptr);
+  std::vector<uint8_t> changed((size_t)P.E, 0);
+  bool any = false;
+  for (int e = 0; e < P.E; ++e) {
+    const int32_t was = h->counted ? h->counts[(size_t)e] : P.N, is = detach ? P.N : counts[e];
+    changed[(size_t)e] = was != is;
+    any = any || was != is;
+  }
+  rvo3d::Cold C = h->live;
+  DeviceGuard dg;
+  if (int rc = dg.enter(h->cfg.device)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int32_t* cdev = h->counts_dev;
+  if (!detach && !cdev) HIP_TRY(hipMalloc((void**)&cdev, align_up((size_t)P.E * 4, 256)));
+  uint8_t* mask = nullptr;
+  if (any && hipMalloc((void**)&mask, (size_t)P.E) != hipSuccess) {
+    if (cdev != h->counts_dev) (void)hipFree(cdev);
+    return fail(RVO3D_ERR_HIP, "rvo3d_set_drone_counts: hipMalloc failed");
+  }
+  C.counts = detach ? nullptr : cdev;
+  C.cnt_two_phase = (!detach && two_phase) ? 1 : 0;
+  // in stream order behind the steps already enqueued: the counts, the parameters, then the reset of the changed envs
+  hipError_t e = hipSuccess;
+  if (!detach) e = hipMemcpyAsync(cdev, counts, (size_t)P.E * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync((void*)P.cold_, &C, sizeof C, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && any) e = hipMemcpyAsync(mask, changed.data(), (size_t)P.E, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && any) {
+    const size_t EN = (size_t)P.E * P.N;
+    hipLaunchKernelGGL(rvo3d::reset_fresh_kernel, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, s, P,
+                       (const uint8_t*)mask);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the host staging and the mask die here
+  if (mask) (void)hipFree(mask);
+  h->counts_dev = cdev;  // (kept for the next attaching call, whatever became of this one)
+  if (e != hipSuccess) {
+    // the device copy of Cold may be the new one already: put back what the handle goes on describing (and the old
+    // counts, which share the array), so that host and device agree again - as far as a failing device lets us
+    if (h->counted) (void)hipMemcpy(cdev, h->counts.data(), (size_t)P.E * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy((void*)P.cold_, &h->live, sizeof h->live, hipMemcpyHostToDevice);
+    h->g_valid = h->dv_valid = false;  // some envs may have been reset
+    return fail(RVO3D_ERR_HIP, std::string("rvo3d_set_drone_counts: ") + hipGetErrorString(e));
+  }
+  h->live = C;
+  h->counted = !detach;
+  h->counts.swap(now);
+  h->cgeo = cgeo;
+  h->ctwo_phase = two_phase;
+  // the stage-G words on file belong to the ring that wrote them, and to the positions before the resets; the des_vel
+  // words of a reset env are its reset state's (reset_drone)
+  h->g_valid = false;
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_drone_counts(rvo3d_env* h, const int32_t** device_counts) {
+  RVO3D_API_BEGIN
+  if (!h || !device_counts) return fail(RVO3D_ERR_INVALID, "null argument");
+  *device_counts = h->counted ? h->counts_dev : nullptr;
   return RVO3D_OK;
   RVO3D_API_END
 }
@@ -596,8 +712,9 @@ int rvo3d_set_routes(rvo3d_env* h, const uint8_t* env_mask, const double* waypoi
   if (int rc = dg.enter(h->cfg.device)) return rc;
   const Params& P = h->P;
   // one workgroup per env: it votes on the env's n_points before its first store
-  hipLaunchKernelGGL(rvo3d::set_routes_kernel, dim3((unsigned)P.E), dim3((unsigned)align_up((size_t)P.N, 64)), 0,
-                     static_cast<hipStream_t>(stream), P, env_mask, waypoints, n_points);
+  hipLaunchKernelGGL(h->counted ? rvo3d::set_routes_counted_kernel : rvo3d::set_routes_kernel, dim3((unsigned)P.E),
+                     dim3((unsigned)align_up((size_t)P.N, 64)), 0, static_cast<hipStream_t>(stream), P, env_mask, waypoints,
+                     n_points);
   HIP_TRY(hipGetLastError());
   h->g_valid = false;  // positions change: the stage-G words on file are stale (the des_vel on file is the reset state's)
   return RVO3D_OK;
@@ -1102,13 +1219,26 @@ int rvo3d_rollout_account(int32_t E, int32_t N, const float* reward, const uint8
                           int32_t* ep_len, uint8_t* cut_slot, uint8_t* extra_mask, double* sums, int32_t* any_extra,
                           void* stream) {
   RVO3D_API_BEGIN
+  return rvo3d_rollout_account_n(E, N, nullptr, reward, done, finish, sanitize, max_ep_len, epoch_end, rew_slot, ep_ret,
+                                 ep_len, cut_slot, extra_mask, sums, any_extra, stream);
+  RVO3D_API_END
+}
+
+int rvo3d_rollout_account_n(int32_t E, int32_t N, const int32_t* drone_counts, const float* reward, const uint8_t* done,
+                            const uint8_t* finish, int32_t sanitize, int32_t max_ep_len, int32_t epoch_end, float* rew_slot,
+                            float* ep_ret, int32_t* ep_len, uint8_t* cut_slot, uint8_t* extra_mask, double* sums,
+                            int32_t* any_extra, void* stream) {
+  RVO3D_API_BEGIN
   if (E < 1 || N < 1 || N > rvo3d::kMaxThreads) return fail(RVO3D_ERR_INVALID, "need num_envs >= 1 and 1 <= num_drones <= 512");
   if (!reward || !done || !finish || !rew_slot || !ep_ret || !ep_len || !cut_slot || !extra_mask || !sums || !any_extra)
     return fail(RVO3D_ERR_INVALID, "null pointer");
   rvo3d::AccountArgs A{E, N, reward, done, finish, sanitize, max_ep_len, epoch_end, rew_slot, ep_ret, ep_len,
                        cut_slot, extra_mask, sums, any_extra, g_step_dev.load()};
-  hipLaunchKernelGGL(rvo3d::rollout_account_kernel, dim3((unsigned)E), dim3((unsigned)align_up((size_t)N, 64)), 0,
-                     static_cast<hipStream_t>(stream), A);
+  const dim3 grid((unsigned)E), block((unsigned)align_up((size_t)N, 64));
+  if (drone_counts)
+    hipLaunchKernelGGL(rvo3d::rollout_account_counted_kernel, grid, block, 0, static_cast<hipStream_t>(stream), A, drone_counts);
+  else
+    hipLaunchKernelGGL(rvo3d::rollout_account_kernel, grid, block, 0, static_cast<hipStream_t>(stream), A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END
@@ -1150,7 +1280,8 @@ int rvo3d_eval_action(rvo3d_env* h, const float* a, float acceler_vel, double* a
   int rc = check(h, true, dg);
   if (rc) return rc;
   const size_t EN = (size_t)h->P.E * h->P.N;
-  hipLaunchKernelGGL(rvo3d::eval_action_kernel, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(h->counted ? rvo3d::eval_action_counted_kernel : rvo3d::eval_action_kernel,
+                     dim3((unsigned)((EN + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), h->P, a, acceler_vel, action64);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
@@ -1174,7 +1305,7 @@ int rvo3d_eval_account(rvo3d_env* h, const float* reward, const uint8_t* done, c
                                  b->ended};
   // eval_lanes_per_env(N) lanes per env: up to 256 envs per workgroup for N = 1, one wave per env from 33 drones on
   const size_t lanes = (size_t)h->P.E * (size_t)rvo3d::eval_lanes_per_env(h->P.N);
-  hipLaunchKernelGGL(rvo3d::eval_account_kernel,
+  hipLaunchKernelGGL(h->counted ? rvo3d::eval_account_counted_kernel : rvo3d::eval_account_kernel,
                      dim3((unsigned)((lanes + rvo3d::kEvalAccountThreads - 1) / rvo3d::kEvalAccountThreads)),
                      dim3(rvo3d::kEvalAccountThreads), 0, static_cast<hipStream_t>(stream), h->P, A);
   HIP_TRY(hipGetLastError());
@@ -1197,7 +1328,8 @@ int rvo3d_des_vel(rvo3d_env* h, double* des_vel, void* stream) {
   if (rc) return rc;
   if (!des_vel) return fail(RVO3D_ERR_INVALID, "des_vel is required");
   const size_t EN = (size_t)h->P.E * h->P.N;
-  hipLaunchKernelGGL(rvo3d::des_vel_kernel, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(h->counted ? rvo3d::des_vel_counted_kernel : rvo3d::des_vel_kernel,
+                     dim3((unsigned)((EN + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), h->P, des_vel);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
@@ -1216,7 +1348,8 @@ int rvo3d_rvo_vel(rvo3d_env* h, const double* vmax, double acceler, double* out_
   for (int k = 0; k < 3; ++k) A.vmax[k] = vmax[k];
   A.acceler = acceler;
   const int T = (int)align_up((size_t)h->P.N, 64);
-  hipLaunchKernelGGL(rvo3d::rvo_vel_kernel, dim3((unsigned)h->P.E), dim3((unsigned)T),
+  hipLaunchKernelGGL(h->counted ? rvo3d::rvo_vel_counted_kernel : rvo3d::rvo_vel_kernel, dim3((unsigned)h->P.E),
+                     dim3((unsigned)T),
                      (size_t)T * 8 * sizeof(double), static_cast<hipStream_t>(stream), h->P, A, out_vel);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
@@ -1312,6 +1445,11 @@ int rvo3d_kernel_name(rvo3d_env* h, int32_t mode, char* buf, int32_t cap) {
   RVO3D_API_BEGIN
   if (!h || !buf || cap < 1) return fail(RVO3D_ERR_INVALID, "null handle / buffer");
   if (mode < 0 || mode > 2) return fail(RVO3D_ERR_INVALID, "mode: 0 observe, 1 step, 2 step + auto-reset");
+  if (h->counted) {
+    std::snprintf(buf, (size_t)cap, "rvo3d::env_kernel_counted<%d, %d, %d, %s>", (int)mode, h->P.nw,
+                  rvo3d::pick_counted_kernel(h->P).nfix, h->P.env_train ? "true" : "false");
+    return RVO3D_OK;
+  }
   const Pick k = pick_kernel(h->P);
   std::snprintf(buf, (size_t)cap, "rvo3d::env_kernel<%d, %d, %d, %s, %s>", (int)mode, h->P.nw, k.nfix,
                 h->P.env_train ? "true" : "false", k.pad ? "true" : "false");
@@ -1323,10 +1461,11 @@ int rvo3d_launch_info(rvo3d_env* h, int32_t* threads, int32_t* envs_per_block, i
                       int32_t* lds_bytes) {
   RVO3D_API_BEGIN
   if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
-  if (threads) *threads = h->geo.threads;
-  if (envs_per_block) *envs_per_block = h->P.epb;
-  if (blocks) *blocks = h->geo.blocks;
-  if (lds_bytes) *lds_bytes = h->geo.lds;
+  const rvo3d::Geometry& G = h->counted ? h->cgeo : h->geo;
+  if (threads) *threads = G.threads;
+  if (envs_per_block) *envs_per_block = h->counted ? (G.threads == 64 ? 64 / rvo3d::pick_counted_kernel(h->P).nfix : 1) : h->P.epb;
+  if (blocks) *blocks = G.blocks;
+  if (lds_bytes) *lds_bytes = G.lds;
   return RVO3D_OK;
   RVO3D_API_END
 }

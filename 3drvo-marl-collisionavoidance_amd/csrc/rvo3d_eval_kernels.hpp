@@ -14,10 +14,19 @@ namespace rvo3d {
 //   action = acceler_vel * a + drone.vel   float32 product, widened, + float64 - and NOT rounded again (the trainer's
 //                                          glue, rvo3d_step.hpp action_mode 1, rounds the sum as well)
 // (-ffp-contract=off keeps the product and the sum apart.)
-__global__ void __launch_bounds__(256) eval_action_kernel(const Params P, const float* a, float acceler_vel,
-                                                          double* action64) {
+// CNT (the *_counted kernels): a handle with drone counts (rvo3d_set_drone_counts) - a ghost's action row is zero,
+// whatever its input row holds.
+template <bool CNT>
+__device__ __forceinline__ void eval_action_body(const Params& P, const float* a, float acceler_vel, double* action64) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= (int64_t)P.E * P.N) return;
+  if (CNT) {
+    const int64_t e = g / P.N;
+    if (g - e * P.N >= P.cold().counts[e]) {
+      action64[g * 3] = 0.0; action64[g * 3 + 1] = 0.0; action64[g * 3 + 2] = 0.0;
+      return;
+    }
+  }
   const float* A = a + g * 3;
   const double vv[3] = {P.vx()[g], P.vy()[g], P.vz()[g]};
 #pragma unroll
@@ -25,6 +34,14 @@ __global__ void __launch_bounds__(256) eval_action_kernel(const Params P, const 
     const float r = __builtin_rintf(A[k] * 100.0f) / 100.0f;
     action64[g * 3 + k] = (double)(acceler_vel * r) + vv[k];
   }
+}
+__global__ void __launch_bounds__(256) eval_action_kernel(const Params P, const float* a, float acceler_vel,
+                                                          double* action64) {
+  eval_action_body<false>(P, a, acceler_vel, action64);
+}
+__global__ void __launch_bounds__(256) eval_action_counted_kernel(const Params P, const float* a, float acceler_vel,
+                                                                  double* action64) {
+  eval_action_body<true>(P, a, acceler_vel, action64);
 }
 
 // ---- episode bookkeeping of one evaluation step (post_train.py:78-105) ----
@@ -104,7 +121,11 @@ struct EvalAccountArgs {
 // L = eval_lanes_per_env(N) consecutive lanes hold one env (64 / L envs per wave, four waves per workgroup); a lane takes
 // the drones l, l + L, ... in order, then the L partial sums meet in a butterfly - an order that depends on N alone, so the
 // float64 speed sum is the same bits in every run.  Lanes beyond E and beyond N stay in the butterfly with neutral values.
-__global__ void __launch_bounds__(kEvalAccountThreads) eval_account_kernel(const Params P, const EvalAccountArgs A) {
+// CNT: the env's drones are its first counts[e]: they alone enter the sums and the flags, and they are summed in the
+// order a handle of counts[e] drones sums them - by its eval_lanes_per_env(counts[e]) lanes, which are the first of this
+// env's lanes; the butterfly's wider steps then only add the other lanes' zeros (x + 0.0 == x for the sums, all >= +0).
+template <bool CNT>
+__device__ __forceinline__ void eval_account_body(const Params P, const EvalAccountArgs A) {
   const int N = P.N;
   const int L = eval_lanes_per_env(N);
   const int64_t slot = ((int64_t)blockIdx.x * kEvalAccountThreads + threadIdx.x) >> __builtin_ctz(L);  // env of this lane group
@@ -113,8 +134,10 @@ __global__ void __launch_bounds__(kEvalAccountThreads) eval_account_kernel(const
   const int64_t e = live ? slot : 0;
   double norm_sum = 0.0;
   int bits = 0;  // 1: a drone collided, 2: a drone has not finished, 4: a drone has not arrived
-  if (live) {
-    for (int d = l; d < N; d += L) {
+  const int Nl = (CNT && live) ? P.cold().counts[e] : N;  // the drones the env has
+  const int Ll = CNT ? eval_lanes_per_env(Nl) : L;
+  if (live && l < Ll) {
+    for (int d = l; d < Nl; d += Ll) {
       const int64_t g = e * N + d;
       const double x = P.vx()[g], y = P.vy()[g], z = P.vz()[g];
       norm_sum += __builtin_sqrt(x * x + y * y + z * z);
@@ -128,7 +151,7 @@ __global__ void __launch_bounds__(kEvalAccountThreads) eval_account_kernel(const
   if (!live || l != 0) return;
   EvalEnvIn in;
   in.ep_len = A.ep_len[e]; in.ep_ret = A.ep_ret[e]; in.speed_sum = A.speed_sum[e]; in.counted = A.counted[e];
-  in.norm_sum = norm_sum; in.n = N; in.reward0 = A.reward[e * N];
+  in.norm_sum = norm_sum; in.n = Nl; in.reward0 = A.reward[e * N];
   in.any_done = (bits & 1) != 0; in.all_finish = (bits & 2) == 0; in.all_info = (bits & 4) == 0;
   in.max_ep_len = A.max_ep_len; in.quota = A.quota;
   const EvalEnvOut o = eval_account_env(in);
@@ -140,6 +163,12 @@ __global__ void __launch_bounds__(kEvalAccountThreads) eval_account_kernel(const
   }
   A.ep_len[e] = o.ep_len; A.ep_ret[e] = o.ep_ret; A.speed_sum[e] = o.speed_sum; A.counted[e] = o.counted;
   A.ended[e] = o.ended ? 1 : 0;
+}
+__global__ void __launch_bounds__(kEvalAccountThreads) eval_account_kernel(const Params P, const EvalAccountArgs A) {
+  eval_account_body<false>(P, A);
+}
+__global__ void __launch_bounds__(kEvalAccountThreads) eval_account_counted_kernel(const Params P, const EvalAccountArgs A) {
+  eval_account_body<true>(P, A);
 }
 
 // ---- row select of rvo3d_observe_envs: one workgroup per env; the envs whose mask byte is zero leave at once, the others

@@ -125,6 +125,60 @@ inline int launch_geometry(int lds_pad, Params& P, Geometry& G, std::string& err
   return RVO3D_OK;
 }
 
+// ---- per-env drone counts (rvo3d_set_drone_counts) ----
+
+constexpr int kMaxCountedDrones = 256;  // the largest compile-time ring
+
+// The argument checks of rvo3d_set_drone_counts (N: the handle's num_drones).  detach: the call asks for full envs again.
+inline int check_drone_counts(int E, int N, const int32_t* counts, bool& detach, std::string& err) {
+  detach = counts == nullptr;
+  if (N > kMaxCountedDrones) {
+    err = "drone counts need num_drones <= 256 (the compile-time rings)";
+    return RVO3D_ERR_INVALID;
+  }
+  if (detach) return RVO3D_OK;
+  for (int e = 0; e < E; ++e)
+    if (counts[e] < 1 || counts[e] > N) {
+      err = "counts entries must be in [1, num_drones]";
+      return RVO3D_ERR_INVALID;
+    }
+  return RVO3D_OK;
+}
+
+// Which instantiation a handle with drone counts runs on: always a padded compile-time ring, the smallest that holds
+// the layout's N rows - 32 lanes up to 32 drones (two envs per wave, also where a plain handle packs up to 32 envs of
+// two drones into one: the price of the counts for small N), 64 up to 64, then pick_kernel's 128 / 192 / 256.
+inline Pick pick_counted_kernel(const Params& P) {
+  if (P.N <= 32) return {32, true};
+  if (P.N <= 64) return {64, true};
+  if (P.N <= 128) return {128, true};
+  if (P.N <= 192) return {192, true};
+  if (P.N <= kMaxCountedDrones) return {256, true};
+  return {0, false};
+}
+
+// Its launch geometry (P: the handle's, with nw = ceil(N / 64) - the ring's as well) and whether the handle's
+// two-phase table (zero_fill_tables: a full workgroup of G's shape) describes its workgroups too.
+inline int counted_geometry(int lds_pad, const Params& P, const Geometry& G, Geometry& out, bool& two_phase,
+                            std::string& err) {
+  const Pick k = pick_counted_kernel(P);
+  if (k.nfix == 0) {
+    err = "drone counts need num_drones <= 256 (the compile-time rings)";
+    return RVO3D_ERR_INVALID;
+  }
+  const int epb = k.nfix <= 64 ? 64 / k.nfix : 1;
+  out.threads = k.nfix <= 64 ? 64 : k.nfix;
+  out.blocks = (P.E + epb - 1) / epb;
+  const size_t lds = lds_bytes(out.threads, P.nm, epb, k.nfix, P.nw) + (size_t)lds_pad;
+  if (lds > 64 * 1024) {
+    err = "neighbors_num * num_drones needs more than 64 KiB of LDS on the counted kernels";
+    return RVO3D_ERR_INVALID;
+  }
+  out.lds = (int)lds;
+  two_phase = epb == P.epb && out.threads == G.threads;
+  return RVO3D_OK;
+}
+
 // The zero-fill index divisor with its magic multiplier, and the two-phase row writer's table.
 inline int zero_fill_tables(const Params& P, int threads, Cold& C, std::string& err) {
   const int N = P.N, epb = P.epb;

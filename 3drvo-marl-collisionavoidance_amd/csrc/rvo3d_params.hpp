@@ -49,6 +49,11 @@ struct Cold {
   // per-env building sets (rvo3d_set_env_buildings): env e reads bld + e * bld_stride (doubles) and
   // bgrid + e * bgrid_stride (u16), nb is nb_max (unused records cannot be hit).  Both 0: the shared list.
   uint32_t bld_stride, bgrid_stride;
+  // per-env drone counts (rvo3d_set_drone_counts): env e has the live drones 0 .. counts[e] - 1 of its N rows; only the
+  // *_counted kernels read the two fields (null / 0 while no counts are attached).  cnt_two_phase: the counted step
+  // runs on the workgroup shape zmask was tabulated for, so the two-phase row writer applies.
+  const int32_t* counts;   // [E], each 1..N
+  int cnt_two_phase;
 };
 constexpr int kBgridK = 15;
 typedef const __attribute__((address_space(4))) Cold ColdC;

@@ -254,7 +254,11 @@ struct AccountArgs {
   uint64_t* step_dev;      // optional: the noise counter of rvo3d_rollout_set_step_counter, advanced by one per call
 };
 
-__global__ void __launch_bounds__(512) rollout_account_kernel(const AccountArgs A) {
+// CNT (rollout_account_counted_kernel, rvo3d_rollout_account_n with counts): env e has the live drones 0 .. counts[e] - 1;
+// a ghost takes no part - its reward-slot and extra-mask bytes are zero, its running values stay, it never times out,
+// never cuts its env's paths and never enters the sums.
+template <bool CNT>
+__device__ __forceinline__ void rollout_account_body(const AccountArgs& A, const int32_t* counts) {
   __shared__ int s_term, s_extra;
   __shared__ double s_sum[8], s_cnt[8];
   const int e = blockIdx.x, d = threadIdx.x;
@@ -262,7 +266,13 @@ __global__ void __launch_bounds__(512) rollout_account_kernel(const AccountArgs 
   if (e == 0 && d == 0 && A.step_dev) *A.step_dev += 1;  // one rollout step done: the next policy call draws new noise
   __syncthreads();
   double my_sum = 0.0, my_cnt = 0.0;
-  if (d < A.N) {
+  const int Nl = CNT ? counts[e] : A.N;
+  if (CNT && d >= Nl && d < A.N) {
+    const int64_t g = (int64_t)e * A.N + d;
+    A.rew_slot[g] = 0.0f;
+    A.extra_mask[g] = 0;
+  }
+  if (d < Nl) {
     const int64_t g = (int64_t)e * A.N + d;
     const float r = A.reward[g];
     const float rf = (r == r && r != __builtin_inff() && r != -__builtin_inff()) ? r : 0.0f;  // nan_to_num(., 0, 0, 0)
@@ -295,6 +305,12 @@ __global__ void __launch_bounds__(512) rollout_account_kernel(const AccountArgs 
     if (s_term || A.epoch_end) A.cut_slot[e] = 1;
     if (s_extra) atomicOr(A.any_extra, 1);
   }
+}
+__global__ void __launch_bounds__(512) rollout_account_kernel(const AccountArgs A) {
+  rollout_account_body<false>(A, nullptr);
+}
+__global__ void __launch_bounds__(512) rollout_account_counted_kernel(const AccountArgs A, const int32_t* counts) {
+  rollout_account_body<true>(A, counts);
 }
 
 // ---- GAE of a finished rollout (multi_PPObuf.finish_path(0) + get, multi_ppo.py:68-91), one lane per column ----

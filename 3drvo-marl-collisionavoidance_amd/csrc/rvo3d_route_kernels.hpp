@@ -18,11 +18,14 @@ namespace rvo3d {
 // n_points before the first store: one entry outside 2..P leaves the env as it was and raises RVO3D_FLAG_BAD_ROUTE.
 constexpr uint32_t kFlagBadRoute = 4u;  // RVO3D_FLAG_BAD_ROUTE (include/rvo3d.h)
 
-__global__ void __launch_bounds__(kMaxThreads) set_routes_kernel(const Params P, const uint8_t* env_mask,
-                                                                 const double* wp_in, const int32_t* np_in) {
+// CNT (set_routes_counted_kernel, a handle with drone counts): the env's live drones alone vote and take their new
+// routes; the ghosts' input rows are not read and their routes stay.
+template <bool CNT>
+__device__ __forceinline__ void set_routes_body(const Params P, const uint8_t* env_mask, const double* wp_in,
+                                                const int32_t* np_in) {
   const int e = blockIdx.x, d = threadIdx.x;
   if (env_mask && !env_mask[e]) return;  // the whole workgroup: no barrier is left behind
-  const bool active = d < P.N;
+  const bool active = d < (CNT ? live_drones(P, e) : P.N);
   const int g = e * P.N + (active ? d : 0);
   const int np = np_in[g];
   if (__syncthreads_or(np < 2 || np > P.P)) {
@@ -46,6 +49,14 @@ __global__ void __launch_bounds__(kMaxThreads) set_routes_kernel(const Params P,
   P.extra_len()[g] = 0.0;
   dv0_drone(P, g);    // reads the rows this lane has just stored
   reset_drone(P, g);
+}
+__global__ void __launch_bounds__(kMaxThreads) set_routes_kernel(const Params P, const uint8_t* env_mask,
+                                                                 const double* wp_in, const int32_t* np_in) {
+  set_routes_body<false>(P, env_mask, wp_in, np_in);
+}
+__global__ void __launch_bounds__(kMaxThreads) set_routes_counted_kernel(const Params P, const uint8_t* env_mask,
+                                                                         const double* wp_in, const int32_t* np_in) {
+  set_routes_body<true>(P, env_mask, wp_in, np_in);
 }
 
 // rvo3d_get_routes: the waypoint rows as stored (padding included), [E][N][P][3]

@@ -113,7 +113,8 @@ class StateView(C.Structure):
 
 
 # every symbol include/rvo3d.h declares (tests check the library exports them all)
-SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_buildings", "rvo3d_set_routes",
+SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_buildings", "rvo3d_set_drone_counts",
+           "rvo3d_drone_counts", "rvo3d_rollout_account_n", "rvo3d_set_routes",
            "rvo3d_get_routes", "rvo3d_sample_routes", "rvo3d_sample_routes_city", "rvo3d_plan_routes", "rvo3d_reset",
            "rvo3d_reset_drones", "rvo3d_observe", "rvo3d_step", "rvo3d_step_autoreset",
            "rvo3d_step_policy", "rvo3d_step_ex", "rvo3d_policy_sample", "rvo3d_policy_mlp_blob_bytes", "rvo3d_policy_mlp_pack",
@@ -150,6 +151,8 @@ def lib():
     L.rvo3d_destroy.argtypes = [vp]
     L.rvo3d_load_world.argtypes = [vp] * 7
     L.rvo3d_set_env_buildings.argtypes = [vp, vp, vp, i32, vp]
+    L.rvo3d_set_drone_counts.argtypes = [vp, vp, vp]
+    L.rvo3d_drone_counts.argtypes = [vp, C.POINTER(vp)]
     L.rvo3d_set_routes.argtypes = [vp, vp, vp, vp, vp]
     L.rvo3d_get_routes.argtypes = [vp, vp, vp, vp]
     L.rvo3d_sample_routes.argtypes = [vp, i32, i32, i32, C.c_uint32, vp, vp, vp, vp, vp]
@@ -186,6 +189,7 @@ def lib():
     L.rvo3d_reader_first_step.argtypes = [C.POINTER(GruReader), vp, C.c_int64, C.c_int64, vp, i32, C.c_int64, vp]
     L.rvo3d_rollout_set_step_counter.argtypes = [vp]
     L.rvo3d_rollout_account.argtypes = [i32, i32, vp, vp, vp, i32, i32, i32] + [vp] * 8
+    L.rvo3d_rollout_account_n.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, i32] + [vp] * 8
     L.rvo3d_gae.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, vp, vp, vp]
     L.rvo3d_eval_action.argtypes = [vp, vp, C.c_float, vp, vp]
     L.rvo3d_eval_account.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_int64, C.POINTER(EvalBufs), vp]

@@ -91,6 +91,12 @@ class BatchedDroneEnv:
         if reward_f64:
             self.reward64 = torch.zeros((E, N), dtype=torch.float64, device=dev)
             _lib.check(L.rvo3d_set_reward_f64(h, _ptr(self.reward64)), "rvo3d_set_reward_f64")
+        # fleets of different sizes (World.drone_counts [E]): attached once the world is loaded
+        self._counts = None  # host copy of the counts in force, None: every env has N drones
+        self._counts_dev = self._live = None
+        self._counts_version = 0  # number of set_drone_counts calls: what a captured launch sequence was made for
+        if getattr(world, "drone_counts", None) is not None:
+            self.set_drone_counts(world.drone_counts)
 
     # -- plumbing ---------------------------------------------------------------
     def _stream(self):
@@ -129,6 +135,53 @@ class BatchedDroneEnv:
                        "rvo3d_set_env_buildings")
         self._env_bld = None if b is None or nb_max == 0 else (b.copy(), None if c is None else c.copy())
         self._dev_bld = None
+
+    def set_drone_counts(self, counts):
+        """Per-env drone counts from the next call on (rvo3d_set_drone_counts): counts [E], each 1..N; env e then has
+        the live drones 0 .. counts[e]-1 and behaves as the env of a BatchedDroneEnv built with those drones alone; the
+        rows beyond are ghosts whose outputs are zeros and whose inputs are ignored.  None: every env has N drones
+        again.  Envs whose count changes end up in their reset state, the others are not touched - e.g. a curriculum
+        that raises the counts between epochs.  Synchronises the current stream.  obs / vo_count are not touched:
+        observe() afterwards."""
+        c = None
+        if counts is not None:
+            c = np.ascontiguousarray(counts.cpu().numpy() if torch.is_tensor(counts) else counts, dtype=np.int32)
+            if c.shape != (self.E,):
+                raise AssertionError(f"counts must have shape ({self.E},)")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().rvo3d_set_drone_counts(self._h, None if c is None else C.c_void_p(c.ctypes.data),
+                                                         self._stream()), "rvo3d_set_drone_counts")
+        self._counts = None if c is None else c.copy()
+        self._counts_dev = self._live = None
+        self._counts_version += 1
+        self._obs_ver = None  # the rows of the envs that changed are stale: the next step writes in full
+
+    @property
+    def drone_counts(self):
+        """The counts in force as a device tensor [E] int32 (a copy of the handle's), or None."""
+        if self._counts is None:
+            return None
+        if self._counts_dev is None:
+            self._counts_dev = torch.from_numpy(self._counts).to(self.device)
+        return self._counts_dev
+
+    def drone_counts_ptr(self):
+        """The handle's own device array of the counts in force (rvo3d_drone_counts) as an address, None without
+        counts.  Unlike the `drone_counts` tensor it stays where it is until close(): what launches that outlive a
+        set_drone_counts (captured graphs) may hold."""
+        ptr = C.c_void_p()
+        _lib.check(_lib.lib().rvo3d_drone_counts(self._h, C.byref(ptr)), "rvo3d_drone_counts")
+        return ptr.value or None
+
+    @property
+    def live(self):
+        """[E, N] bool on the device: True for the drones an env has (all True without counts).  Cached."""
+        if self._live is None:
+            if self._counts is None:
+                self._live = torch.ones((self.E, self.N), dtype=torch.bool, device=self.device)
+            else:
+                self._live = torch.arange(self.N, device=self.device)[None, :] < self.drone_counts[:, None]
+        return self._live
 
     def device_buildings(self):
         """What the env collides with now, as device tensors: (buildings [1, nb, 4] - the world's shared list - or
@@ -377,6 +430,8 @@ class BatchedDroneEnv:
         if self._routes_set:
             wp, npts = self.routes()
             sd["waypoints"], sd["n_points"] = wp.cpu(), npts.cpu()
+        if self._counts is not None:
+            sd["drone_counts"] = torch.from_numpy(self._counts.copy())
         return sd
 
     def load_state_dict(self, sd):
@@ -384,9 +439,16 @@ class BatchedDroneEnv:
         if shape != [self.E, self.N, self.P, self.nm]:
             raise ValueError(f"checkpoint is for E,N,P,nm = {shape}, this env has "
                              f"{[self.E, self.N, self.P, self.nm]}")
-        if "waypoints" in sd:  # the routes first: set_routes resets every drone, the state below follows them
+        # the routes on full envs (with counts attached set_routes would leave the ghosts' routes as they are, and a later
+        # set_drone_counts that raises a count would fly them), then the counts: both reset drones, the state below
+        # follows them
+        if "waypoints" in sd:
+            if self._counts is not None:
+                self.set_drone_counts(None)
             self.set_routes(sd["waypoints"], sd["n_points"])
-        self.set_state(**{k: v for k, v in sd.items() if k not in ("shape", "waypoints", "n_points")})
+        if "drone_counts" in sd or self._counts is not None:
+            self.set_drone_counts(sd.get("drone_counts"))
+        self.set_state(**{k: v for k, v in sd.items() if k not in ("shape", "waypoints", "n_points", "drone_counts")})
 
     def error_flags(self) -> int:
         """Reads and clears the device error word (synchronises)."""

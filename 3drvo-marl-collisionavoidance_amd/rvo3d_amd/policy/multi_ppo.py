@@ -139,9 +139,11 @@ def gae_device(rew, val, cut, gamma=0.99, lam=0.97):
 
 class RolloutBuffer:
     """[T, E, N, ...] storage on the device (the batched multi_PPObuf, multi_ppo.py:39-94).  fused_gae=True: get()
-    computes the advantages with `gae_device` (one HIP launch) where the buffer is on a GPU; a CPU buffer ignores it."""
+    computes the advantages with `gae_device` (one HIP launch) where the buffer is on a GPU; a CPU buffer ignores it.
+    live: [E, N] bool, the drones the envs have (BatchedDroneEnv.live of an env with drone counts), or None: get()
+    then hands out the live rows only - the ghost rows of the storage hold zeros and the policy's answer to them."""
 
-    def __init__(self, T, E, N, obs_width, act_dim, device, gamma=0.99, lam=0.95, fused_gae=False):
+    def __init__(self, T, E, N, obs_width, act_dim, device, gamma=0.99, lam=0.95, fused_gae=False, live=None):
         f32 = dict(dtype=torch.float32, device=device)
         # T + 1 observation slots: slot t is what the policy saw at step t; the env writes the
         # observation after step t straight into slot t + 1 (no copies in the rollout loop)
@@ -154,6 +156,7 @@ class RolloutBuffer:
         self.cut = torch.zeros((T, E), dtype=torch.bool, device=device)
         self.gamma, self.lam, self.ptr, self.T = gamma, lam, 0, T
         self.fused_gae = bool(fused_gae)
+        self.live = None if live is None else torch.as_tensor(live, dtype=torch.bool, device=device).reshape(E, N)
 
     def store(self, obs, cnt, act, rew, val, logp):
         assert self.ptr < self.T  # multi_ppo.py:59
@@ -178,9 +181,17 @@ class RolloutBuffer:
         self.ptr = 0
         self.cut.zero_()
         flat = lambda x: x.reshape((-1,) + x.shape[3:])
-        return dict(obs=flat(self.obs[:self.T]), cnt=flat(self.cnt[:self.T]), act=flat(self.act),
+        if self.live is not None:
+            # the live rows, still ordered t, e, n (GAE runs per column: the ghost columns touch nobody's numbers)
+            rows = self.live.unsqueeze(0).expand(self.rew.shape).reshape(-1)
+            full = flat
+            flat = lambda x: full(x)[rows]
+        data = dict(obs=flat(self.obs[:self.T]), cnt=flat(self.cnt[:self.T]), act=flat(self.act),
                     ret=flat(ret), adv=flat(adv), logp=flat(self.logp),
                     shape=tuple(self.rew.shape))  # (T, E, N): rows are ordered t, e, n
+        if self.live is not None:
+            data["live"] = self.live  # [E, N]: which of the T E N rows of `shape` the data holds
+        return data
 
 
 class multi_ppo:
@@ -259,7 +270,11 @@ class multi_ppo:
             dist.get_rank() if (dist is not None and dist.is_initialized()) else 0)) & 0xFFFFFFFFFFFFFFFF
         torch.manual_seed(seed + (dist.get_rank() if (dist is not None and dist.is_initialized()) else 0))
         self.E, self.N = env.E, env.N
-        self.robot_num = env.N  # env.ir_gym.drone_num (multi_ppo.py:110)
+        # fleets of different sizes (BatchedDroneEnv.set_drone_counts): the [E, N] mask of the drones the envs have, None
+        # without counts.  Fixed for the trainer's buffer: set_drone_counts between epochs goes with set_live()
+        self.live = env.live if getattr(env, "drone_counts", None) is not None else None
+        # env.ir_gym.drone_num (multi_ppo.py:110); with counts: the largest fleet
+        self.robot_num = env.N if self.live is None else int(self.live.sum(dim=1).max())
         self.device = env.device
         # the shared reader sits in both optimizers, as in the reference (multi_ppo.py:115-116)
         pi_params = self.ac.pi.parameters() if hasattr(self.ac.pi, "parameters") else \
@@ -292,10 +307,28 @@ class multi_ppo:
         self.amp = amp
         self.nonfinite_rewards = 0
         self.buf = RolloutBuffer(steps_per_epoch, self.E, self.N, env.W, 3, self.device, gamma, lam,
-                                 fused_gae=self.fused_gae)
+                                 fused_gae=self.fused_gae, live=self.live)
         self.ep_len = torch.zeros((self.E, self.N), dtype=torch.int32, device=self.device)
         self.ep_ret = torch.zeros((self.E, self.N), dtype=torch.float32, device=self.device)
         self.log = []
+
+    def set_live(self):
+        """Takes over the env's drone counts after a BatchedDroneEnv.set_drone_counts between two epochs (a curriculum):
+        the buffer's live mask, robot_num, and the running episode values of the rows that are ghosts now; observes the
+        env (the envs whose count changed were reset) and starts the next rollout from that observation; drops the
+        captured rollout graphs (they hold the step kernel and the bookkeeping's counts by value).  collect() refuses to
+        run on counts it has not been told about."""
+        env = self.env
+        env.observe()
+        self.__dict__.pop("_cur", None)
+        if getattr(self, "_graphs", None):
+            self._graphs.clear()
+        self.live = env.live if env.drone_counts is not None else None
+        self.buf.live = self.live
+        self.robot_num = env.N if self.live is None else int(self.live.sum(dim=1).max())
+        if self.live is not None:
+            self.ep_len.masked_fill_(~self.live, 0)
+            self.ep_ret.masked_fill_(~self.live, 0.0)
 
     # ---- rollout ------------------------------------------------------------------------
     def _fused_mode(self):
@@ -461,6 +494,9 @@ class multi_ppo:
             _lib.check(L.rvo3d_policy_sample(C.byref(hd), E * N, 1.0, self._sample_seed, ac["step"], *map(p, out), None,
                                              None, stream()), "rvo3d_policy_sample")
 
+        # the ghosts take no part in the bookkeeping: the handle's own counts array ([E] int32, where it is until the env
+        # is closed - a captured launch may hold its address) or None
+        counts = self._counts_ptr()
         policy = {"direct": policy_direct, "heads": policy_heads}.get(
             mode, lambda x, cnt, out: kernel_step.launch(x, cnt, *out, 1.0, self._sample_seed, step_arg()))
 
@@ -469,18 +505,20 @@ class multi_ppo:
             ac["step"] += 1  # (the noise counter: one per step in every mode)
             # the env steps from the stored (rounded) action: rounding twice is rounding once
             env.step_policy(buf.act[t], autoreset=True, obs_out=buf.obs[t + 1], cnt_out=buf.cnt[t + 1])
-            _lib.check(L.rvo3d_rollout_account(E, N, p(env.reward), p(env.done), p(env.finish),
-                                               1 if self.sanitize_rewards else 0, int(self.max_ep_len),
-                                               1 if epoch_ended else 0, p(buf.rew[t]), p(self.ep_ret), p(self.ep_len),
-                                               p(ac["cut"][t]), p(ac["extra"]), p(ac["sums"]), p(ac["any_extra"]),
-                                               stream()), "rvo3d_rollout_account")
+            _lib.check(L.rvo3d_rollout_account_n(E, N, None if counts is None else C.c_void_p(counts), p(env.reward), p(env.done),
+                                                 p(env.finish), 1 if self.sanitize_rewards else 0, int(self.max_ep_len),
+                                                 1 if epoch_ended else 0, p(buf.rew[t]), p(self.ep_ret), p(self.ep_len),
+                                                 p(ac["cut"][t]), p(ac["extra"]), p(ac["sums"]), p(ac["any_extra"]),
+                                                 stream()), "rvo3d_rollout_account_n")
 
         def one_step(t, epoch_ended):
             if not use_graph or getattr(self, "_graph_failed", False):
                 return launches(t, epoch_ended)
             key = (mode, t, bool(epoch_ended), T, buf.obs.data_ptr(), buf.act.data_ptr(), buf.logp.data_ptr(),
                    buf.val.data_ptr(), buf.rew.data_ptr(), buf.cnt.data_ptr(), ac["cut"].data_ptr(),
-                   kernel_step.blob_ptr, env.obs.data_ptr(), id(env))
+                   kernel_step.blob_ptr, env.obs.data_ptr(), id(env),
+                   # which step kernel runs and whose counts the bookkeeping reads are part of a captured launch
+                   getattr(env, "_counts_version", 0), counts)
             g = self._graphs.get(key)
             if g is None:
                 if len(self._graphs) > 4 * T + 8:
@@ -524,7 +562,18 @@ class multi_ppo:
             # (~500 rows per step at 64 x 4096: ~0.1 ms of that kernel) goes back to the library-GEMM path
             self._rnn0_dense = float((buf.cnt[:T] > 0).float().mean()) > 2e-3
         s = ac["sums"].sum(dim=0).tolist()
+        self.last_rollout = dict(ret_sum=float(s[0]), episodes=int(s[1]))  # the statistic's two halves
         return float(s[0] / max(s[1], 1.0))
+
+    def _counts_ptr(self):
+        """The address of the env's counts for rvo3d_rollout_account_n (None without counts); a trainer whose live mask is
+        not the env's - set_drone_counts without set_live() - must not collect: its buffer and bookkeeping would take
+        ghosts for drones or drones for ghosts."""
+        env = self.env
+        counted = getattr(env, "drone_counts", None) is not None
+        if (self.live is not None) != counted or (counted and self.live is not env.live):
+            raise RuntimeError("the env's drone counts changed: call set_live() before the next collect()")
+        return env.drone_counts_ptr() if counted else None
 
     def _reset_extra(self, extra, epoch_ended):
         """The resets the fused step left to the trainer (timeouts; at the epoch's end everybody it did not reset) - or,
@@ -542,6 +591,7 @@ class multi_ppo:
         env writes each observation straight into the next buffer slot; the policy GEMMs run
         under ONE autocast region (weight casts are cached across the steps).
         final_reset=False (rollout_profile only) leaves out the epoch-end full reset."""
+        self._counts_ptr()  # (refuses drone counts the trainer has not been told about: set_live())
         if self._fused_ok():
             return self._collect_fused(final_reset)
         env, buf = self.env, self.buf
@@ -551,6 +601,9 @@ class multi_ppo:
         ret_n = torch.zeros((), device=self.device)
         since_full_reset = 0  # no episode can be longer than this: timeouts need no device check before
         hundred = torch.full((self.E, self.N, 3), 100.0, dtype=torch.float32, device=self.device)
+        # drone counts: the ghosts take no part (what rvo3d_rollout_account_n does on the fused path) - their episode
+        # values stay zero, they never time out, never end a path and never enter the statistic
+        live = self.live
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16, enabled=self.amp):
             for t in range(self.steps_per_epoch):
                 obs, cnt = buf.obs[t], buf.cnt[t]
@@ -569,15 +622,15 @@ class multi_ppo:
                 buf.val[t].copy_(v.view(self.E, self.N))
                 buf.logp[t].copy_(logp.view(self.E, self.N))
                 buf.ptr += 1
-                self.ep_ret += rew_fin
-                self.ep_len += 1
+                self.ep_ret += rew_fin  # (a ghost's reward is +0.0)
+                self.ep_len += 1 if live is None else live.to(torch.int32)
                 since_full_reset += 1
                 epoch_ended = final_reset and t == self.steps_per_epoch - 1
                 reset_by_step = (done | fin) != 0        # what the fused step already reset
                 if epoch_ended:                          # full reset (multi_ppo.py:244-264)
-                    ended = torch.ones_like(reset_by_step)
+                    ended = torch.ones_like(reset_by_step) if live is None else live.clone()
                     terminal = torch.ones(self.E, dtype=torch.bool, device=self.device)
-                    extra = ~reset_by_step
+                    extra = ~reset_by_step if live is None else ~reset_by_step & live
                 elif since_full_reset > self.max_ep_len:  # only now can an episode time out
                     timeout = self.ep_len > self.max_ep_len
                     ended = reset_by_step | timeout
@@ -596,6 +649,7 @@ class multi_ppo:
                 self.ep_ret.masked_fill_(ended, 0.0)
                 self.ep_len.masked_fill_(ended, 0)
         self._cur = (buf.obs[self.steps_per_epoch], buf.cnt[self.steps_per_epoch])
+        self.last_rollout = dict(ret_sum=float(ret_sum), episodes=int(ret_n))  # the statistic's two halves
         return float(ret_sum / ret_n.clamp(min=1))
 
     def rollout_profile(self, steps=4):
@@ -655,7 +709,8 @@ class multi_ppo:
         unweighted."""
         if self._world() == 1:
             return
-        n = torch.tensor([self.E * self.N, -(self.E * self.N)], dtype=torch.int64, device=self.device)
+        rows = self.E * self.N if self.live is None else int(self.live.sum())  # the samples an epoch gives the update
+        n = torch.tensor([rows, -rows], dtype=torch.int64, device=self.device)
         self.dist.all_reduce(n, op=self.dist.ReduceOp.MAX)
         if int(n[0]) != -int(n[1]):
             raise ValueError(f"ranks own different shard sizes (max {int(n[0])}, min {-int(n[1])} "
@@ -744,12 +799,20 @@ class multi_ppo:
         if self.reference_order:
             T, E, N = data["shape"]
             per_agent = []
+            live = data.get("live")
+            if live is not None:
+                # agent r = drone r of the envs that have one (counts[e] > r), all steps: the data holds the live rows in
+                # t, e, n order, `drone` is each row's n
+                drone = torch.arange(N, device=live.device).expand(T, E, N)[live.unsqueeze(0).expand(T, E, N)]
+                for r in range(int(live.sum(dim=1).max())):
+                    per_agent.append({k: v[drone == r] for k, v in data.items() if k not in ("shape", "live")})
+                return self._update_reference_order(per_agent)
             for r in range(N):  # agent r = drone r of every env, all steps
                 pick = lambda x: x.reshape((T, E, N) + tuple(x.shape[1:]))[:, :, r].reshape(
                     (T * E,) + tuple(x.shape[1:]))
                 per_agent.append({k: pick(v) for k, v in data.items() if k != "shape"})
             return self._update_reference_order(per_agent)
-        data = {k: v for k, v in data.items() if k != "shape"}
+        data = {k: v for k, v in data.items() if k not in ("shape", "live")}
         n = data["adv"].shape[0]
         kl, pi_steps = 0.0, 0
         for i in range(self.train_pi_iters):  # multi_ppo.py:355-368

@@ -168,6 +168,10 @@ class post_train:
         counted = [0] * E
         total = quota * E
         check_domain = not getattr(env, "env_train", True)
+        # drone counts (BatchedDroneEnv.set_drone_counts): the reductions over an env's drones range over the drones it
+        # has, as rvo3d_eval_account makes them on the fused path; `ghost` is None without counts
+        counts = getattr(env, "drone_counts", None)
+        ghost = None if counts is None else ~env.live
         while n < total:
             if act_fn is not None:
                 a = act_fn(obs.view(-1, env.W), cnt.view(-1)).view(E, N, 3)
@@ -179,10 +183,15 @@ class post_train:
             else:
                 action = env.des_vel()
             obs, cnt, rew, done, info, fin = env.step(action)             # plain drone_step
-            speed_sum += torch.linalg.vector_norm(env.vel, dim=-1).mean(dim=1)
+            if ghost is None:
+                speed_sum += torch.linalg.vector_norm(env.vel, dim=-1).mean(dim=1)
+                all_fin, all_info = fin.bool().all(dim=1), info.bool().all(dim=1)
+            else:
+                speed_sum += torch.linalg.vector_norm(env.vel, dim=-1).masked_fill(ghost, 0.0).sum(dim=1) / counts.double()
+                all_fin, all_info = (fin.bool() | ghost).all(dim=1), (info.bool() | ghost).all(dim=1)
             ep_ret += rew[:, 0].double()                                   # r[0] (post_train.py:82)
             ep_len += 1
-            ended = done.bool().any(dim=1) | (ep_len == self.max_ep_len) | fin.bool().all(dim=1)
+            ended = done.bool().any(dim=1) | (ep_len == self.max_ep_len) | all_fin   # (a ghost's done byte is 0)
             if check_domain:
                 # ONE read of the (read-and-clear) error word per step; both bits are acted on here, so
                 # nothing is lost to the clear.  With E > 1 the word is not attributed to an env: the
@@ -194,8 +203,7 @@ class post_train:
                 if flags & 1:
                     raise ValueError("observation contains NaN/Inf")  # ir_gym.py:232-239
             if bool(ended.any()):
-                arrived = info.bool().all(dim=1)
-                success = fin.bool().all(dim=1)
+                arrived, success = all_info, all_fin
                 idx = torch.nonzero(ended).flatten().tolist()
                 el, sp, er = ep_len.cpu().numpy(), (speed_sum / ep_len.double()).cpu().numpy(), ep_ret.cpu().numpy()
                 ar, su = arrived.cpu().numpy(), success.cpu().numpy()

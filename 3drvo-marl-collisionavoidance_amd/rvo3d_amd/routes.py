@@ -15,6 +15,10 @@ minimum separation).  The result is DEFINED by the rules below, so that a wave c
    ends, c_d is min_len from start_d.  A drone still unplaced after the last round keeps its last candidate.
 4. Starts first, then ends; unplaced[e] counts the drones left unplaced, starts plus ends.
 
+Drone counts (BatchedDroneEnv.set_drone_counts): RouteSampler and CityRoutePlanner draw and plan for all N lanes of an env;
+set_routes takes the live rows' routes and leaves the ghosts' unused ones as they are, so a live drone's route does not
+depend on its env's count.
+
 Env e of a batch draws from counter word e + env_offset: a shard whose env_offset is its first env
 (sharding.shard_env_range) holds the routes the whole batch would.
 

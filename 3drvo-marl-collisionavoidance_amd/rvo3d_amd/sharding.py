@@ -42,6 +42,13 @@ def shard_env_range(total_envs: int, rank: int, world: int):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def shard_world(world, rank: int, world_size: int):
+    """Rank's contiguous block of a World's envs (shard_env_range), with everything that belongs to an env: routes,
+    per-env building sets and drone counts."""
+    lo, hi = shard_env_range(world.shape[0], rank, world_size)
+    return world.select(slice(lo, hi))
+
+
 def init_process_group(backend: str, device=None):
     import torch.distributed as dist
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")

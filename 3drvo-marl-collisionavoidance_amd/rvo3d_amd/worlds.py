@@ -19,10 +19,26 @@ class World:
     buildings: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))
     # per-env sets only: [E] int32, env e's set is buildings[e, :building_counts[e]] (None: all nb_max)
     building_counts: np.ndarray | None = None
+    # fleets of different sizes: [E] int32, env e has the drones 0 .. drone_counts[e]-1 of its N rows, the rows beyond
+    # are ghosts (BatchedDroneEnv.set_drone_counts); None: every env has N drones
+    drone_counts: np.ndarray | None = None
 
     @property
     def shape(self):
         return self.waypoints.shape[:3]
+
+    def env_drones(self, e: int) -> int:
+        """The drones env e has."""
+        return int(self.shape[1] if self.drone_counts is None else self.drone_counts[e])
+
+    def with_drone_counts(self, counts) -> "World":
+        """The same world with env e cut down to its first counts[e] drones (each 1..N; None: all N again)."""
+        c = None
+        if counts is not None:
+            c = np.array(counts, dtype=np.int32)
+            if c.shape != (self.shape[0],) or np.any(c < 1) or np.any(c > self.shape[1]):
+                raise ValueError("with_drone_counts: counts must be [E] with entries in 1..N")
+        return World(self.waypoints, self.n_points, self.map_size, self.buildings, self.building_counts, c)
 
     @property
     def per_env_buildings(self) -> bool:
@@ -47,14 +63,16 @@ class World:
         k = min(p, P)
         used = np.arange(k)[None, None, :, None] < np.asarray(self.n_points)[:, :, None, None]
         out[:, :, :k] = np.where(used, wp[:, :, :k], out[:, :, :k])
-        return World(out, np.array(self.n_points, dtype=np.int32), self.map_size, self.buildings, self.building_counts)
+        return World(out, np.array(self.n_points, dtype=np.int32), self.map_size, self.buildings, self.building_counts,
+                     self.drone_counts)
 
     def select(self, envs) -> "World":
         """The world of the listed envs (indices, a slice or a mask over E); a shared list stays shared."""
         per = self.per_env_buildings
         cnt = self.building_counts[envs] if per and self.building_counts is not None else None
         return World(self.waypoints[envs], self.n_points[envs], self.map_size,
-                     self.buildings[envs] if per else self.buildings, cnt)
+                     self.buildings[envs] if per else self.buildings, cnt,
+                     None if self.drone_counts is None else np.asarray(self.drone_counts)[envs])
 
 
 def world_from_dict(d: dict, num_envs: int = 1) -> World:
@@ -117,39 +135,51 @@ def synthetic_world(E: int, N: int, map_size, n_points: int = 2, nb: int = 0, se
     return World(wp, np.full((E, N), n_points, np.int32), np.asarray(map_size, dtype=np.float64), bld)
 
 
-def stack_worlds(worlds) -> World:
-    """One batch of several worlds, concatenated along E: equal drone counts and map sizes (ValueError otherwise),
-    shorter routes padded with the destination.  The buildings stay one shared list when every world brings the
-    same one; otherwise each env gets the list of the world it came from (building_counts where the lengths differ)."""
+def stack_worlds(worlds, pad_drones: bool = False) -> World:
+    """One batch of several worlds, concatenated along E: equal map sizes (ValueError otherwise), shorter routes padded
+    with the destination.  Worlds of different drone counts are a ValueError too unless pad_drones: then every env is
+    padded to the largest count with copies of its drone 0 route (n_points 2) and drone_counts [E] says how many
+    drones each env has (None when they all have the same) - the padding rows are ghosts, never stepped.  The buildings
+    stay one shared list when every world brings the same one; otherwise each env gets the list of the world it came
+    from (building_counts where the lengths differ)."""
     worlds = list(worlds)
     if not worlds:
         raise ValueError("stack_worlds needs at least one world")
-    N, m = worlds[0].shape[1], np.asarray(worlds[0].map_size, dtype=np.float64)
+    N, m = max(w.shape[1] for w in worlds), np.asarray(worlds[0].map_size, dtype=np.float64)
     for w in worlds:
-        if w.shape[1] != N:
-            raise ValueError("stack_worlds: the worlds have different drone counts")
+        if w.shape[1] != N and not pad_drones:
+            raise ValueError("stack_worlds: the worlds have different drone counts (pad_drones=True pads them)")
         if not np.array_equal(np.asarray(w.map_size, dtype=np.float64), m):
             raise ValueError("stack_worlds: the worlds have different map sizes")
     P = max(w.shape[2] for w in worlds)
-    wps = []
+    wps, nps = [], []
     for w in worlds:
         wp = np.asarray(w.waypoints, dtype=np.float64)
-        E, p = wp.shape[0], wp.shape[2]
+        npt = np.asarray(w.n_points, dtype=np.int32)
+        E, n, p = wp.shape[:3]
         if p < P:  # pad with each drone's destination, wp[e, i, n_points - 1]
-            last = np.take_along_axis(wp, (np.asarray(w.n_points).astype(np.int64) - 1)[:, :, None, None], axis=2)
-            wp = np.concatenate([wp, np.broadcast_to(last, (E, N, P - p, 3))], axis=2)
+            last = np.take_along_axis(wp, (npt.astype(np.int64) - 1)[:, :, None, None], axis=2)
+            wp = np.concatenate([wp, np.broadcast_to(last, (E, n, P - p, 3))], axis=2)
+        if n < N:  # ghost rows: the env's drone 0 route, cut to its first leg
+            ghost = wp[:, :1].copy()
+            ghost[:, :, 2:] = ghost[:, :, 1:2]
+            wp = np.concatenate([wp, np.broadcast_to(ghost, (E, N - n, P, 3))], axis=1)
+            npt = np.concatenate([npt, np.full((E, N - n), 2, np.int32)], axis=1)
         wps.append(wp)
+        nps.append(npt)
     wp = np.concatenate(wps, 0)
-    npts = np.concatenate([np.asarray(w.n_points, dtype=np.int32) for w in worlds], 0)
+    npts = np.concatenate(nps, 0)
+    dcnt = np.concatenate([np.asarray([w.env_drones(e) for e in range(w.shape[0])], dtype=np.int32) for w in worlds])
+    dcnt = None if np.all(dcnt == N) else dcnt
     lists = [np.asarray(w.env_buildings(e), dtype=np.float64).reshape(-1, 4) for w in worlds for e in range(w.shape[0])]
     if all(l.shape == lists[0].shape and np.array_equal(l, lists[0]) for l in lists):
-        return World(wp, npts, m, lists[0].copy())
+        return World(wp, npts, m, lists[0].copy(), None, dcnt)
     nb_max = max(len(l) for l in lists)
     bld = np.zeros((len(lists), nb_max, 4))
     for e, l in enumerate(lists):
         bld[e, :len(l)] = l
     cnt = np.asarray([len(l) for l in lists], dtype=np.int32)
-    return World(wp, npts, m, bld, None if np.all(cnt == nb_max) else cnt)
+    return World(wp, npts, m, bld, None if np.all(cnt == nb_max) else cnt, dcnt)
 
 
 def crossing_world(E: int, N: int, map_size, radius: float | None = None, alt_spread: float = 1.0,

@@ -109,6 +109,34 @@ int rvo3d_load_world(rvo3d_env *h, const double *waypoints, const int32_t *n_poi
  * before the first HIP call; a refused call leaves the handle as it was. */
 int rvo3d_set_env_buildings(rvo3d_env *h, const double *buildings, const int32_t *counts, int32_t nb_max, void *stream);
 
+/* Per-env drone counts: fleets of different sizes in one handle.  HOST counts [E], each 1..num_drones; NULL detaches
+ * (every env has num_drones again).  Env e has the live drones 0 .. counts[e]-1; the rows d >= counts[e] are ghosts.  All
+ * layouts stay [E][num_drones].  Env e behaves bit for bit as the env of a handle created with num_drones = counts[e] and
+ * loaded with the first counts[e] routes, radii and priorities - state, observations, vo_count, rewards (float32, and
+ * float64 when attached), flags, reset_mask and the error word - through every handle-bound entry point: observe, the
+ * four step entry points, reset, reset_drones, observe_envs, des_vel, rvo_vel, eval_action, eval_account, set_routes and
+ * get_state / set_state.
+ * Ghost rows of every output are defined, and written by every call that writes the live rows (a buffer slot never keeps
+ * stale data): the observation row is all zeros; vo_count, reward (+0.0), done, info, finish and reset_mask are 0; the
+ * des_vel, rvo_vel and eval_action rows are 0.  Ghost rows of the inputs - actions, drone_mask bytes, the waypoints and
+ * n_points of rvo3d_set_routes - are ignored, NaN and out-of-range values included (a bad n_points in a ghost row does
+ * not raise RVO3D_FLAG_BAD_ROUTE).  Ghost rows of the state arrays hold the reset state of their unused route and never
+ * change (rvo3d_set_state excepted: what it writes there is never read).  The prev_vo_count promise (rvo3d_step_args)
+ * keeps its meaning.  rvo3d_eval_account divides `speed` by counts[e]; "all info", "all finish" and "any done" range over
+ * the live drones.  The route samplers and the planner draw for all num_drones lanes: the ghosts' routes are unused.
+ * Needs a loaded world (RVO3D_ERR_STATE otherwise); a later rvo3d_load_world drops the counts.  num_drones <= 256 (the
+ * compile-time rings; RVO3D_ERR_INVALID beyond).  A counted handle of up to 32 drones steps two envs per workgroup on a
+ * 32-lane ring, one of up to 64 drones one env on a 64-lane ring: where neighbors_num is so large that this needs more than
+ * 64 KiB of LDS the call is refused (RVO3D_ERR_INVALID), although the plain handle may run.  A HIP failure inside the call
+ * (RVO3D_ERR_HIP) leaves the counts that were in force in force, but envs may have been reset.  Every env whose count changes ends up in its reset state, as
+ * rvo3d_reset leaves it - with extra_len = 0, so that it equals the env of a freshly loaded handle in every state field -
+ * and what the step keeps on file is marked stale; envs whose count does not change are not
+ * touched.  May allocate and synchronises, like rvo3d_set_env_buildings; step and observe still allocate nothing.  Every
+ * argument check runs before the first HIP call; a refused call leaves the handle as it was. */
+int rvo3d_set_drone_counts(rvo3d_env *h, const int32_t *counts, void *stream);
+/* DEVICE pointer to the counts in force ([E] int32, handle-owned), NULL while none are attached. */
+int rvo3d_drone_counts(rvo3d_env *h, const int32_t **device_counts);
+
 /* New routes for the envs whose mask byte is non-zero, from DEVICE memory: waypoints [E][N][P][3] (routes shorter than P
  * padded with anything), n_points [E][N] (each 2..P), env_mask [E] (NULL = every env; the other two are required).  A
  * masked env ends up exactly as an env of a handle freshly loaded (rvo3d_load_world) with these routes: the waypoint rows
@@ -481,6 +509,13 @@ int rvo3d_rollout_account(int32_t num_envs, int32_t num_drones, const float *rew
                           const uint8_t *finish, int32_t sanitize, int32_t max_ep_len, int32_t epoch_end,
                           float *rew_slot, float *ep_ret, int32_t *ep_len, uint8_t *cut_slot,
                           uint8_t *extra_mask, double *sums, int32_t *any_extra, void *stream);
+/* ... with per-env drone counts: drone_counts is a DEVICE pointer [E] (what rvo3d_drone_counts hands out), NULL = the call
+ * above.  Env e's rows d >= drone_counts[e] are ghosts and take no part: their rew_slot and extra_mask bytes are 0, their
+ * ep_len / ep_ret stay as they are (0), they never time out, never set cut_slot and never enter sums. */
+int rvo3d_rollout_account_n(int32_t num_envs, int32_t num_drones, const int32_t *drone_counts, const float *reward,
+                            const uint8_t *done, const uint8_t *finish, int32_t sanitize, int32_t max_ep_len,
+                            int32_t epoch_end, float *rew_slot, float *ep_ret, int32_t *ep_len, uint8_t *cut_slot,
+                            uint8_t *extra_mask, double *sums, int32_t *any_extra, void *stream);
 
 /* multi_PPObuf.finish_path(0) + get (train/policy/multi_ppo.py:68-91) for every column of a [T][E][N] rollout in ONE
  * launch: rew / val / adv / ret [steps][envs][drones] float32, cut [steps][envs] bytes (any non-zero byte: the paths of

@@ -8,7 +8,9 @@ then
 
 A kernel's text runs from its label to the end of its "Kernel info" comment block (code, kernel descriptor, resource
 usage).  Local labels (.LBB<n>_<m> and BB<n>_<m> in comments, .Lfunc_end<n>, .Ltmp<n>) are replaced by a constant, since they count functions
-across the whole file.  For a kernel that differs the script prints the resource lines and the counts of the
+across the whole file, and the blanks in front of a trailing comment by one (the assembler aligns those comments behind
+the label, whose length changes with the numbers).  A kernel of NEW that OLD does not have is listed and does not count
+(--strict: it does).  For a kernel that differs the script prints the resource lines and the counts of the
 instructions that decide speed for both builds and the head of a unified diff.  Exit status 1 if any kernel differs
 or exists on one side only.
 """
@@ -21,6 +23,7 @@ import sys
 
 BEGIN = re.compile(r"^\s*\.protected\s+(\S+)\s*; -- Begin function")
 LABEL = re.compile(r"(\.L)?BB\d+_\d+|\.Lfunc_(begin|end)\d+|\.Ltmp\d+")
+COMMENT_GAP = re.compile(r"(?<=\S)[ \t]+;")
 RESOURCE = ("TotalNumSgprs", "NumVgprs", "NumAgprs", "TotalNumVgprs", "ScratchSize", "LDSByteSize", "Occupancy",
             "codeLenInByte")
 COUNTED = ("v_mfma", "buffer_load", "global_load", "ds_read", "ds_write", "s_waitcnt", "s_barrier", "scratch_")
@@ -42,7 +45,7 @@ def kernels(path):
             if info and not line.startswith(";"):
                 cur = None  # (behind the resource comments: the next function's section directives)
                 continue
-            cur.append(LABEL.sub(".L", line.rstrip("\n")))
+            cur.append(COMMENT_GAP.sub(" ;", LABEL.sub(".L", line.rstrip("\n"))))
     return out
 
 
@@ -76,6 +79,7 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--only", default="", help="compare only kernels whose demangled name contains this")
     ap.add_argument("--diff-lines", type=int, default=80, help="lines of unified diff printed per differing kernel")
+    ap.add_argument("--strict", action="store_true", help="a kernel that only NEW has counts as a difference too")
     a = ap.parse_args()
     old, new = kernels(a.old), kernels(a.new)
     names = demangle(sorted(set(old) | set(new)))
@@ -85,7 +89,7 @@ def main():
             continue
         if sym not in old or sym not in new:
             print(f"ONLY IN {'OLD' if sym in old else 'NEW'}  {nice}")
-            bad += 1
+            bad += 1 if (sym in old or a.strict) else 0
             continue
         if old[sym] == new[sym]:
             print(f"identical  {nice}")
