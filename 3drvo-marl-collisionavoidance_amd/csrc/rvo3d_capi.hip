@@ -77,6 +77,9 @@ struct rvo3d_env {
   rvo3d::Geometry cgeo{};       // launch geometry of the counted step
   bool ctwo_phase = false;      // Cold::cnt_two_phase while attached
   int lds_pad = 0;              // diagnostics build only: the extra LDS bytes of every step launch (0 in the product)
+  // rvo3d_eval_account_safety: the scan's per-env step values, [E] doubles x 3 then [E] int32; allocated by the first
+  // rvo3d_load_world and kept until rvo3d_destroy
+  double* safety_scratch = nullptr;
 };
 
 namespace {
@@ -509,6 +512,7 @@ int rvo3d_destroy(rvo3d_env* h) {
   (void)hipDeviceSynchronize();
   if (h->env_bld) (void)hipFree(h->env_bld);
   if (h->counts_dev) (void)hipFree(h->counts_dev);
+  if (h->safety_scratch) (void)hipFree(h->safety_scratch);
   if (h->arena) (void)hipFree(h->arena);
   delete h;
   return RVO3D_OK;
@@ -531,6 +535,7 @@ int rvo3d_load_world(rvo3d_env* h, const double* waypoints, const int32_t* n_poi
   rvo3d::StagedWorld w;
   std::string err;
   if (int rc2 = rvo3d::stage_world(h->P, waypoints, n_points, radius, priority, w, err)) return fail(rc2, err);
+  if (!h->safety_scratch) HIP_TRY(hipMalloc((void**)&h->safety_scratch, align_up((size_t)P.E * (3 * 8 + 4), 256)));
   // a new world drops per-env building sets and drone counts: the shared list and full envs are in force again (the
   // sets' allocation goes at the end)
   if (h->env_bld || h->counted) HIP_TRY(hipMemcpyAsync((void*)P.cold_, &C, sizeof C, hipMemcpyHostToDevice, s));
@@ -1288,26 +1293,108 @@ int rvo3d_eval_action(rvo3d_env* h, const float* a, float acceler_vel, double* a
   RVO3D_API_END
 }
 
-int rvo3d_eval_account(rvo3d_env* h, const float* reward, const uint8_t* done, const uint8_t* info, const uint8_t* finish,
-                       int32_t max_ep_len, int32_t quota, int64_t step, const rvo3d_eval_bufs* b, void* stream) {
-  RVO3D_API_BEGIN
-  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+}  // extern "C"
+
+namespace {
+// rvo3d_eval_account and rvo3d_eval_account_safety: the same checks (before the first HIP call), arguments and grid
+int check_eval_account_args(const float* reward, const uint8_t* done, const uint8_t* info, const uint8_t* finish,
+                            int32_t max_ep_len, int32_t quota, const rvo3d_eval_bufs* b) {
   if (!reward || !done || !info || !finish || !b) return fail(RVO3D_ERR_INVALID, "null pointer");
   if (!b->ep_len || !b->ep_ret || !b->speed_sum || !b->counted || !b->rec_len || !b->rec_ret || !b->rec_speed ||
       !b->rec_step || !b->rec_flags || !b->remaining || !b->ended)
     return fail(RVO3D_ERR_INVALID, "null pointer in rvo3d_eval_bufs");
   if (max_ep_len < 1 || quota < 1) return fail(RVO3D_ERR_INVALID, "need max_ep_len >= 1 and quota >= 1");
+  return RVO3D_OK;
+}
+rvo3d::EvalAccountArgs eval_account_args(const float* reward, const uint8_t* done, const uint8_t* info,
+                                         const uint8_t* finish, int32_t max_ep_len, int32_t quota, int64_t step,
+                                         const rvo3d_eval_bufs* b) {
+  return {reward, done, info, finish, max_ep_len, quota, step, b->ep_len, b->ep_ret, b->speed_sum,
+          b->counted, b->rec_len, b->rec_ret, b->rec_speed, b->rec_step, b->rec_flags, b->remaining, b->ended};
+}
+// eval_lanes_per_env(N) lanes per env: up to 256 envs per workgroup for N = 1, one wave per env from 33 drones on
+dim3 eval_account_grid(const rvo3d_env* h) {
+  const size_t lanes = (size_t)h->P.E * (size_t)rvo3d::eval_lanes_per_env(h->P.N);
+  return dim3((unsigned)((lanes + rvo3d::kEvalAccountThreads - 1) / rvo3d::kEvalAccountThreads));
+}
+}  // namespace
+
+extern "C" {
+
+int rvo3d_eval_account(rvo3d_env* h, const float* reward, const uint8_t* done, const uint8_t* info, const uint8_t* finish,
+                       int32_t max_ep_len, int32_t quota, int64_t step, const rvo3d_eval_bufs* b, void* stream) {
+  RVO3D_API_BEGIN
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (int rc = check_eval_account_args(reward, done, info, finish, max_ep_len, quota, b)) return rc;
   DeviceGuard dg;
   int rc = check(h, true, dg);
   if (rc) return rc;
-  const rvo3d::EvalAccountArgs A{reward, done, info, finish, max_ep_len, quota, step, b->ep_len, b->ep_ret, b->speed_sum,
-                                 b->counted, b->rec_len, b->rec_ret, b->rec_speed, b->rec_step, b->rec_flags, b->remaining,
-                                 b->ended};
-  // eval_lanes_per_env(N) lanes per env: up to 256 envs per workgroup for N = 1, one wave per env from 33 drones on
-  const size_t lanes = (size_t)h->P.E * (size_t)rvo3d::eval_lanes_per_env(h->P.N);
-  hipLaunchKernelGGL(h->counted ? rvo3d::eval_account_counted_kernel : rvo3d::eval_account_kernel,
-                     dim3((unsigned)((lanes + rvo3d::kEvalAccountThreads - 1) / rvo3d::kEvalAccountThreads)),
-                     dim3(rvo3d::kEvalAccountThreads), 0, static_cast<hipStream_t>(stream), h->P, A);
+  hipLaunchKernelGGL(h->counted ? rvo3d::eval_account_counted_kernel : rvo3d::eval_account_kernel, eval_account_grid(h),
+                     dim3(rvo3d::kEvalAccountThreads), 0, static_cast<hipStream_t>(stream), h->P,
+                     eval_account_args(reward, done, info, finish, max_ep_len, quota, step, b));
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+}  // extern "C"
+
+namespace {
+// the scan's launch for both entry points below (arguments checked, device entered)
+int launch_safety_scan(rvo3d_env* h, const rvo3d::SafetyArgs& A, hipStream_t s) {
+  const int N = h->P.N, T = rvo3d::safety_threads(N);
+  const size_t epb = (size_t)(T / rvo3d::safety_lanes_per_env(N));
+  hipLaunchKernelGGL(h->counted ? rvo3d::safety_scan_counted_kernel : rvo3d::safety_scan_kernel,
+                     dim3((unsigned)(((size_t)h->P.E + epb - 1) / epb)), dim3((unsigned)T), rvo3d::safety_lds_bytes(N), s,
+                     h->P, A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+}
+bool near_margin_ok(double m) { return std::isfinite(m) && m >= 0.0; }
+}  // namespace
+
+extern "C" {
+
+int rvo3d_safety_scan(rvo3d_env* h, double near_margin, double* sep, double* bclear, double* wall, int32_t* near_pairs,
+                      void* stream) {
+  RVO3D_API_BEGIN
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!near_margin_ok(near_margin)) return fail(RVO3D_ERR_INVALID, "near_margin must be finite and >= 0");
+  if (!sep && !bclear && !wall && !near_pairs) return fail(RVO3D_ERR_INVALID, "at least one output is required");
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const rvo3d::SafetyArgs A{near_margin, sep, bclear, wall, near_pairs, nullptr, nullptr, nullptr};
+  return launch_safety_scan(h, A, static_cast<hipStream_t>(stream));
+  RVO3D_API_END
+}
+
+int rvo3d_eval_account_safety(rvo3d_env* h, const float* reward, const uint8_t* done, const uint8_t* info,
+                              const uint8_t* finish, int32_t max_ep_len, int32_t quota, int64_t step,
+                              const rvo3d_eval_bufs* b, double near_margin, const rvo3d_eval_safety_bufs* sb,
+                              void* stream) {
+  RVO3D_API_BEGIN
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (int rc = check_eval_account_args(reward, done, info, finish, max_ep_len, quota, b)) return rc;
+  if (!near_margin_ok(near_margin)) return fail(RVO3D_ERR_INVALID, "near_margin must be finite and >= 0");
+  if (!sb) return fail(RVO3D_ERR_INVALID, "null pointer");
+  if (!sb->ep_min_sep || !sb->ep_min_bclear || !sb->ep_min_wall || !sb->ep_near || !sb->rec_min_sep ||
+      !sb->rec_min_bclear || !sb->rec_min_wall || !sb->rec_near)
+    return fail(RVO3D_ERR_INVALID, "null pointer in rvo3d_eval_safety_bufs");
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t E = (size_t)h->P.E;
+  double* st = h->safety_scratch;  // (rvo3d_load_world allocated it)
+  int32_t* st_near = reinterpret_cast<int32_t*>(st + 3 * E);
+  const rvo3d::SafetyArgs A{near_margin, nullptr, nullptr, nullptr, st_near, st, st + E, st + 2 * E};
+  if (int rc2 = launch_safety_scan(h, A, s)) return rc2;
+  const rvo3d::EvalSafetyArgs S{st, st + E, st + 2 * E, st_near, sb->ep_min_sep, sb->ep_min_bclear, sb->ep_min_wall,
+                                sb->ep_near, sb->rec_min_sep, sb->rec_min_bclear, sb->rec_min_wall, sb->rec_near, quota};
+  hipLaunchKernelGGL(h->counted ? rvo3d::eval_account_safety_counted_kernel : rvo3d::eval_account_safety_kernel,
+                     eval_account_grid(h), dim3(rvo3d::kEvalAccountThreads), 0, s, h->P,
+                     eval_account_args(reward, done, info, finish, max_ep_len, quota, step, b), S);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END

@@ -124,8 +124,13 @@ struct EvalAccountArgs {
 // CNT: the env's drones are its first counts[e]: they alone enter the sums and the flags, and they are summed in the
 // order a handle of counts[e] drones sums them - by its eval_lanes_per_env(counts[e]) lanes, which are the first of this
 // env's lanes; the butterfly's wider steps then only add the other lanes' zeros (x + 0.0 == x for the sums, all >= +0).
-template <bool CNT>
-__device__ __forceinline__ void eval_account_body(const Params P, const EvalAccountArgs A) {
+// `extra(e, counted before this step, decision)` runs on the env's deciding lane behind the decision: nothing here,
+// the safety fold of rvo3d_safety_kernels.hpp for rvo3d_eval_account_safety.
+struct EvalNoExtra {
+  __device__ __forceinline__ void operator()(int64_t, int32_t, const EvalEnvOut&) const {}
+};
+template <bool CNT, class Extra>
+__device__ __forceinline__ void eval_account_body(const Params P, const EvalAccountArgs A, const Extra extra) {
   const int N = P.N;
   const int L = eval_lanes_per_env(N);
   const int64_t slot = ((int64_t)blockIdx.x * kEvalAccountThreads + threadIdx.x) >> __builtin_ctz(L);  // env of this lane group
@@ -163,12 +168,13 @@ __device__ __forceinline__ void eval_account_body(const Params P, const EvalAcco
   }
   A.ep_len[e] = o.ep_len; A.ep_ret[e] = o.ep_ret; A.speed_sum[e] = o.speed_sum; A.counted[e] = o.counted;
   A.ended[e] = o.ended ? 1 : 0;
+  extra(e, in.counted, o);
 }
 __global__ void __launch_bounds__(kEvalAccountThreads) eval_account_kernel(const Params P, const EvalAccountArgs A) {
-  eval_account_body<false>(P, A);
+  eval_account_body<false>(P, A, EvalNoExtra{});
 }
 __global__ void __launch_bounds__(kEvalAccountThreads) eval_account_counted_kernel(const Params P, const EvalAccountArgs A) {
-  eval_account_body<true>(P, A);
+  eval_account_body<true>(P, A, EvalNoExtra{});
 }
 
 // ---- row select of rvo3d_observe_envs: one workgroup per env; the envs whose mask byte is zero leave at once, the others

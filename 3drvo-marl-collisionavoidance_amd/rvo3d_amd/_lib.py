@@ -106,6 +106,12 @@ class EvalBufs(C.Structure):
                                           "rec_step", "rec_flags", "remaining", "ended")]
 
 
+class EvalSafetyBufs(C.Structure):
+    """rvo3d_eval_safety_bufs (rvo3d_eval_account_safety)."""
+    _fields_ = [(n, C.c_void_p) for n in ("ep_min_sep", "ep_min_bclear", "ep_min_wall", "ep_near", "rec_min_sep",
+                                          "rec_min_bclear", "rec_min_wall", "rec_near")]
+
+
 class StateView(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("px", "py", "pz", "vx", "vy", "vz", "yaw", "pitch", "real_len", "max_dev",
@@ -123,7 +129,7 @@ SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_b
            "rvo3d_policy_rnn_tiles_blob_bytes", "rvo3d_policy_rnn_tiles_pack", "rvo3d_policy_rnn_tiles_work_bytes",
            "rvo3d_policy_rnn_tiles", "rvo3d_policy_rnn_tiles_x3_blob_bytes", "rvo3d_policy_rnn_tiles_x3_pack",
            "rvo3d_policy_rnn_tiles_x3", "rvo3d_reader_first_step", "rvo3d_rollout_account", "rvo3d_rollout_set_step_counter", "rvo3d_gae",
-           "rvo3d_eval_action", "rvo3d_eval_account", "rvo3d_observe_envs", "rvo3d_set_reward_f64",
+           "rvo3d_eval_action", "rvo3d_eval_account", "rvo3d_safety_scan", "rvo3d_eval_account_safety", "rvo3d_observe_envs", "rvo3d_set_reward_f64",
            "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
 
@@ -193,6 +199,9 @@ def lib():
     L.rvo3d_gae.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, vp, vp, vp]
     L.rvo3d_eval_action.argtypes = [vp, vp, C.c_float, vp, vp]
     L.rvo3d_eval_account.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_int64, C.POINTER(EvalBufs), vp]
+    L.rvo3d_safety_scan.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp]
+    L.rvo3d_eval_account_safety.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_int64, C.POINTER(EvalBufs), C.c_double,
+                                            C.POINTER(EvalSafetyBufs), vp]
     L.rvo3d_observe_envs.argtypes = [vp] * 7
     L.rvo3d_des_vel.argtypes = [vp, vp, vp]
     L.rvo3d_rvo_vel.argtypes = [vp, C.POINTER(C.c_double), C.c_double, vp, vp]

@@ -364,6 +364,22 @@ class BatchedDroneEnv:
         self._keep_a = a
         return self._action64
 
+    def safety(self, near_margin: float = 0.5):
+        """Safety metrics of the current state (rvo3d_safety_scan; the rules are in include/rvo3d.h): (sep, bclear, wall
+        float64 [E, N], near_pairs int32 [E]) - per drone the gap to the nearest other drone of its env, to the
+        buildings that reach up to it and to the map faces (<= 0, <= 0 and < 0: what `done` reports), per env the
+        pairs within near_margin of touching.  Ghost rows are +inf.  Call it behind a plain step(): behind
+        step(autoreset=True) a reset env shows its reset state.  The env's persistent tensors, overwritten by the next
+        call; one launch, no synchronisation."""
+        if getattr(self, "_safety", None) is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            self._safety = (torch.empty((self.E, self.N), **f64), torch.empty((self.E, self.N), **f64),
+                            torch.empty((self.E, self.N), **f64), torch.empty(self.E, dtype=torch.int32, device=self.device))
+        s = self._safety
+        _lib.check(_lib.lib().rvo3d_safety_scan(self._h, float(near_margin), _ptr(s[0]), _ptr(s[1]), _ptr(s[2]), _ptr(s[3]),
+                                                self._stream()), "rvo3d_safety_scan")
+        return s
+
     def des_vel(self):
         out = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
         _lib.check(_lib.lib().rvo3d_des_vel(self._h, _ptr(out), self._stream()), "rvo3d_des_vel")

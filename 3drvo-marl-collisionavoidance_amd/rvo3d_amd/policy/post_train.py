@@ -33,6 +33,13 @@ the observation of its step (ir_gym.observation_reward, with the action).  The u
 re-observes EVERY env with action = 0 (ir_gym.env_observation) whenever any env ended, so with
 E > 1 and a policy that looks at its observation an env's trajectory there depends on its
 neighbours' episode ends; with E = 1 the two loops agree.
+
+safety=True (opt-in, either loop) adds the safety figures of the field to the result: per episode the minimum separation
+between two drones, the minimum clearance to a building and to a map face, and the near-miss pair-steps (pairs within
+near_margin of touching), from rvo3d_safety_scan on the state behind every step (the rules: include/rvo3d.h).  The fused
+loop calls rvo3d_eval_account_safety in place of rvo3d_eval_account, which folds them into four more record arrays on
+the device; the host loop calls env.safety() and folds by the same rules.  `policy_test` returns what it returns
+without it and leaves the summary (rvo3d_amd.safety.summarize_safety) in self.safety.
 """
 from __future__ import annotations
 
@@ -42,6 +49,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..safety import summarize_safety
 from .policy_step import KernelPolicyStep
 
 # bits of a record's flag byte (rvo3d_eval_account)
@@ -83,17 +91,22 @@ def summarize_records(step, env, length, ret, speed, flags, policy_name="policy"
 class post_train:
     def __init__(self, env, num_episodes=100, max_ep_len=150, acceler_vel=1.0, render=False,
                  save=False, neighbor_region=4, neighbor_num=5, args=None, fused=False, policy_kernel=None,
-                 poll_every=8, seed=0, **kwargs):
+                 poll_every=8, seed=0, safety=False, near_margin=0.5, **kwargs):
         """fused: the device-side loop (module docstring); policy_kernel: None (policy.step_tensors) or the
         KernelPolicyStep kind that runs the policy - "mlp", "mlp_x3" (the MLP actor-critic, bf16 / float32-class),
         "rnn_tiles" or "rnn_tiles_x3" (the biGRU actor-critic, likewise) - either loop; poll_every: steps between two host
-        reads of the fused loop; seed: of the kernels' counter-based noise."""
+        reads of the fused loop; seed: of the kernels' counter-based noise; safety / near_margin: the safety figures (module
+        docstring), off by default: neither loop then makes a launch it did not make before."""
         if policy_kernel not in (None, "mlp", "mlp_x3", "rnn_tiles", "rnn_tiles_x3"):
             raise ValueError("policy_kernel must be None, 'mlp', 'mlp_x3', 'rnn_tiles' or 'rnn_tiles_x3', "
                              f"not {policy_kernel!r}")
         if int(poll_every) < 1:
             raise ValueError("poll_every must be >= 1")
         self.fused, self.policy_kernel, self.poll_every, self.seed = bool(fused), policy_kernel, int(poll_every), int(seed)
+        self.with_safety, self.near_margin = bool(safety), float(near_margin)
+        if not (np.isfinite(self.near_margin) and self.near_margin >= 0.0):
+            raise ValueError("near_margin must be finite and >= 0")
+        self.safety = None   # summarize_safety's dict once policy_test ran with safety=True
         self.env = env
         self.num_episodes = num_episodes
         self.max_ep_len = max_ep_len
@@ -172,6 +185,11 @@ class post_train:
         # has, as rvo3d_eval_account makes them on the fused path; `ghost` is None without counts
         counts = getattr(env, "drone_counts", None)
         ghost = None if counts is None else ~env.live
+        if self.with_safety:   # running minima / near pair-steps of every env's episode, folded as rvo3d_eval_account_safety folds
+            inf = torch.full((E,), float("inf"), dtype=torch.float64, device=dev)
+            run = [inf.clone(), inf.clone(), inf.clone(), torch.zeros(E, dtype=torch.int64, device=dev)]
+            safety_records = []   # (min_sep, min_bclear, min_wall, near, drones) per counted episode
+            drones_of = np.full(E, N) if counts is None else counts.cpu().numpy()
         while n < total:
             if act_fn is not None:
                 a = act_fn(obs.view(-1, env.W), cnt.view(-1)).view(E, N, 3)
@@ -192,6 +210,12 @@ class post_train:
             ep_ret += rew[:, 0].double()                                   # r[0] (post_train.py:82)
             ep_len += 1
             ended = done.bool().any(dim=1) | (ep_len == self.max_ep_len) | all_fin   # (a ghost's done byte is 0)
+            if self.with_safety:   # the state behind the step, before any reset; ghost rows are +inf
+                s_sep, s_bclear, s_wall, s_near = env.safety(self.near_margin)
+                for k, v in enumerate((s_sep, s_bclear, s_wall)):
+                    m = v.min(dim=1).values
+                    run[k] = torch.where(m < run[k], m, run[k])
+                run[3] = run[3] + s_near.to(torch.int64)
             if check_domain:
                 # ONE read of the (read-and-clear) error word per step; both bits are acted on here, so
                 # nothing is lost to the clear.  With E > 1 the word is not attributed to an env: the
@@ -207,6 +231,8 @@ class post_train:
                 idx = torch.nonzero(ended).flatten().tolist()
                 el, sp, er = ep_len.cpu().numpy(), (speed_sum / ep_len.double()).cpu().numpy(), ep_ret.cpu().numpy()
                 ar, su = arrived.cpu().numpy(), success.cpu().numpy()
+                if self.with_safety:
+                    rs = [r.cpu().numpy() for r in run]
                 for e in idx:
                     if counted[e] >= quota:
                         continue  # this env has delivered its share; it keeps stepping, uncounted
@@ -215,6 +241,8 @@ class post_train:
                         print("%s, Episode %d \t EpRet %.3f \t EpLen %d \t EpSpeed  %.3f"
                               % ("Successful" if ar[e] else "Fail", n, er[e], el[e], sp[e]))
                     records.append((el[e], er[e], sp[e], (REC_ARRIVED if ar[e] else 0) | (REC_FINISHED if su[e] else 0)))
+                    if self.with_safety:
+                        safety_records.append((rs[0][e], rs[1][e], rs[2][e], rs[3][e], drones_of[e]))
                     n += 1
                 env.reset(ended)
                 obs, cnt = env.observe()
@@ -222,7 +250,13 @@ class post_train:
                 ep_len = torch.where(ended, z, ep_len)
                 ep_ret = torch.where(ended, torch.zeros_like(ep_ret), ep_ret)
                 speed_sum = torch.where(ended, torch.zeros_like(speed_sum), speed_sum)
+                if self.with_safety:
+                    run = [torch.where(ended, inf, r) for r in run[:3]] + [torch.where(ended, torch.zeros_like(run[3]), run[3])]
         length, ret, speed, flags = zip(*records)
+        if self.with_safety:
+            ms, mb, mw, nr, dr = (np.asarray(x) for x in zip(*safety_records))
+            self.safety_records = dict(rec_min_sep=ms, rec_min_bclear=mb, rec_min_wall=mw, rec_near=nr)
+            self.safety = summarize_safety(ms, mb, mw, nr, length, dr)
         result, line, _ = summarize_records(np.arange(n), np.zeros(n, dtype=np.int64), length, ret, speed, flags, policy_name)
         if result_path is not None:
             with open(result_path + result_name, "a") as f:
@@ -244,6 +278,15 @@ class post_train:
                  rec_flags=z((E, quota), torch.uint8), remaining=torch.full((1,), total, dtype=torch.int32, device=dev),
                  ended=z(E, torch.uint8))
         bufs = _lib.EvalBufs(**{k: v.data_ptr() for k, v in t.items()})
+        rec_keys = ("rec_step", "rec_len", "rec_ret", "rec_speed", "rec_flags")
+        if self.with_safety:
+            inf = lambda shape: torch.full(shape, float("inf"), dtype=torch.float64, device=dev)
+            ts = dict(ep_min_sep=inf((E,)), ep_min_bclear=inf((E,)), ep_min_wall=inf((E,)), ep_near=z(E, torch.int64),
+                      rec_min_sep=inf((E, quota)), rec_min_bclear=inf((E, quota)), rec_min_wall=inf((E, quota)),
+                      rec_near=z((E, quota), torch.int64))
+            sbufs = _lib.EvalSafetyBufs(**{k: v.data_ptr() for k, v in ts.items()})
+            t.update({k: v for k, v in ts.items() if k.startswith("rec_")})
+            rec_keys += ("rec_min_sep", "rec_min_bclear", "rec_min_wall", "rec_near")
         L = _lib.lib()
         p = lambda x: C.c_void_p(x.data_ptr())
         check_domain = not getattr(env, "env_train", True)
@@ -257,8 +300,13 @@ class post_train:
             else:
                 action = env.des_vel()
             obs, cnt, rew, done, info, fin = env.step(action)             # plain drone_step
-            _lib.check(L.rvo3d_eval_account(env._h, p(rew), p(done), p(info), p(fin), self.max_ep_len, quota, step,
-                                            C.byref(bufs), env._stream()), "rvo3d_eval_account")
+            if self.with_safety:
+                _lib.check(L.rvo3d_eval_account_safety(env._h, p(rew), p(done), p(info), p(fin), self.max_ep_len, quota,
+                                                       step, C.byref(bufs), self.near_margin, C.byref(sbufs),
+                                                       env._stream()), "rvo3d_eval_account_safety")
+            else:
+                _lib.check(L.rvo3d_eval_account(env._h, p(rew), p(done), p(info), p(fin), self.max_ep_len, quota, step,
+                                                C.byref(bufs), env._stream()), "rvo3d_eval_account")
             env.reset(t["ended"])
             obs, cnt = env.observe_envs(t["ended"])
             step += 1
@@ -273,7 +321,12 @@ class post_train:
                     break
         e_idx = np.repeat(np.arange(E), quota)   # env of record [e][k]; remaining <= 0: every slot is filled
         # the records as the device left them, [E][quota] each (kept for the caller: self.records)
-        rec = self.records = {k: t[k].cpu().numpy() for k in ("rec_step", "rec_len", "rec_ret", "rec_speed", "rec_flags")}
+        rec = self.records = {k: t[k].cpu().numpy() for k in rec_keys}
+        if self.with_safety:
+            counts = getattr(env, "drone_counts", None)
+            drones = np.repeat(np.full(E, N) if counts is None else counts.cpu().numpy(), quota)
+            self.safety = summarize_safety(rec["rec_min_sep"], rec["rec_min_bclear"], rec["rec_min_wall"], rec["rec_near"],
+                                           rec["rec_len"].reshape(-1), drones)
         flat = {k: v.reshape(-1) for k, v in rec.items()}
         result, line, episode_lines = summarize_records(flat["rec_step"], e_idx, flat["rec_len"], flat["rec_ret"],
                                                         flat["rec_speed"], flat["rec_flags"], policy_name)

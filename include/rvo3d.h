@@ -115,7 +115,7 @@ int rvo3d_set_env_buildings(rvo3d_env *h, const double *buildings, const int32_t
  * loaded with the first counts[e] routes, radii and priorities - state, observations, vo_count, rewards (float32, and
  * float64 when attached), flags, reset_mask and the error word - through every handle-bound entry point: observe, the
  * four step entry points, reset, reset_drones, observe_envs, des_vel, rvo_vel, eval_action, eval_account, set_routes and
- * get_state / set_state.
+ * get_state / set_state; rvo3d_safety_scan and rvo3d_eval_account_safety likewise (their ghost rows are +inf, see there).
  * Ghost rows of every output are defined, and written by every call that writes the live rows (a buffer slot never keeps
  * stale data): the observation row is all zeros; vo_count, reward (+0.0), done, info, finish and reset_mask are 0; the
  * des_vel, rvo_vel and eval_action rows are 0.  Ghost rows of the inputs - actions, drone_mask bytes, the waypoints and
@@ -569,6 +569,60 @@ typedef struct rvo3d_eval_bufs {
 int rvo3d_eval_account(rvo3d_env *h, const float *reward, const uint8_t *done, const uint8_t *info,
                        const uint8_t *finish, int32_t max_ep_len, int32_t quota, int64_t step,
                        const rvo3d_eval_bufs *bufs, void *stream);
+
+/* Safety metrics of the handle's CURRENT state: how close the drones are to each other, to the buildings and to the map
+ * faces.  In the evaluator that is the state behind a plain rvo3d_step and before any reset; behind an auto-resetting step
+ * the state of an env that was reset is its reset state, so the approach that ended the episode is no longer there.
+ * DEVICE outputs, any of them NULL (not computed), but not all four: sep, bclear, wall [E][N] float64, near_pairs [E]
+ * int32.  The result is defined by these rules, to the last bit; every value is a float64, every operation rounded on its
+ * own (no FMA), a square is x * x, sqrt is correctly rounded.  Env e has the live drones 0 .. n_e-1, n_e = num_drones or,
+ * on a counted handle (rvo3d_set_drone_counts), counts[e]; p is a drone's position, r its radius.
+ *   1. sep[e][i] = min over the live j != i (by index, not by position) of dis_ij - (r_i + r_j), with rel = p_j - p_i and
+ *      dis_ij = sqrt((rel_y*rel_y + rel_x*rel_x) + rel_z*rel_z) (the order of rvo_inter.py's `dis`); +inf in an env of
+ *      one live drone.  sep <= 0 holds exactly when dis <= r_i + r_j: the reference's pair collision with env_train = 1
+ *      (rvo_inter.py:144).
+ *   2. bclear[e][i] = min over the buildings b = (x_b, y_b, h_b, r_b) env e collides with now - its per-env set of
+ *      counts[e] records when sets are attached (rvo3d_set_env_buildings), else the shared list - that have p_z <= h_b
+ *      (check_col_with_budilding, rvo_inter.py:198-209) of d - (r_i + r_b), d = sqrt(ex*ex + ey*ey), ex = p_x - x_b,
+ *      ey = p_y - y_b; +inf when no building counts.  bclear <= 0 is the reference's building hit (but for its 5 m gate,
+ *      which can only matter where r_i + r_b > 5).
+ *   3. wall[e][i] = m + 0.0, m = the minimum over the axes k = 0, 1, 2 of p_k and of map_k - p_k.  wall < 0 holds exactly
+ *      when drone_out_map is true (drone.py:213-225).  (The + 0.0 turns the -0.0 of a coordinate that is -0.0 into +0.0:
+ *      no output is ever -0.0.)
+ *   4. near_pairs[e] = the number of unordered live pairs i < j with dis_ij - (r_i + r_j) <= near_margin, colliding pairs
+ *      included.  near_margin is finite and >= 0 (RVO3D_ERR_INVALID otherwise).
+ *   5. A minimum starts from +inf and takes x < m ? x : m.  For finite positions no candidate is NaN and none is -0.0, so
+ *      the three minima, like the integer count, do not depend on the order of evaluation: the result is the same bits
+ *      for every launch geometry.
+ *   6. Ghost rows (d >= n_e) of sep, bclear and wall are written as +inf by every call, so that a min over a row needs no
+ *      mask - a deliberate exception to the zeros every other output holds in its ghost rows.  Ghost rows of the state
+ *      are never read.
+ * One lane per drone, the env's positions and radii staged in LDS once, the buildings in tiles; fleets of up to 64
+ * drones share a wave (several envs per wave), larger ones take one workgroup per env.  One launch: no allocation, no
+ * synchronisation, no atomics.  Needs a loaded world (RVO3D_ERR_STATE); every argument check runs before the first HIP
+ * call and a refused call writes nothing. */
+int rvo3d_safety_scan(rvo3d_env *h, double near_margin, double *sep, double *bclear, double *wall,
+                      int32_t *near_pairs, void *stream);
+
+/* rvo3d_eval_account with the safety metrics folded into the episode records.  What it does to `bufs` is exactly what
+ * rvo3d_eval_account does (the same per-env decision, the same kernel body).  In addition, per env, with this step's
+ * values s = (min over the env's live drones of sep, of bclear, of wall; near_pairs) from rvo3d_safety_scan's rules on the
+ * current state (after the step, before any reset): folded = (min(s.sep, ep_min_sep), min(s.bclear, ep_min_bclear),
+ * min(s.wall, ep_min_wall), ep_near + s.near_pairs), minima by rule 5; where rvo3d_eval_account stores a record, the four
+ * folded values go to the same slot of rec_*; an env whose episode ended goes on with (+inf, +inf, +inf, 0), any other
+ * with the folded values.  sbufs: HOST struct of device pointers; the caller sets the running values to +inf and 0 before
+ * the first call.  Two launches: the scan, into per-env scratch the handle owns (allocated by rvo3d_load_world: this call
+ * allocates nothing), and the account.  Arguments and checks as rvo3d_eval_account, near_margin as rvo3d_safety_scan. */
+typedef struct rvo3d_eval_safety_bufs {
+  double *ep_min_sep, *ep_min_bclear, *ep_min_wall;   /* [E] running, +inf before the first call */
+  int64_t *ep_near;                                   /* [E] running sum of near_pairs, 0 before */
+  double *rec_min_sep, *rec_min_bclear, *rec_min_wall;/* [E][quota] records                      */
+  int64_t *rec_near;                                  /* [E][quota]                              */
+} rvo3d_eval_safety_bufs;
+int rvo3d_eval_account_safety(rvo3d_env *h, const float *reward, const uint8_t *done, const uint8_t *info,
+                              const uint8_t *finish, int32_t max_ep_len, int32_t quota, int64_t step,
+                              const rvo3d_eval_bufs *bufs, double near_margin,
+                              const rvo3d_eval_safety_bufs *sbufs, void *stream);
 
 /* rvo3d_observe for the envs whose mask byte is non-zero (env_mask [E], required): their rows of obs / vo_count receive
  * bit for bit what rvo3d_observe writes, the other envs' rows are not written at all - an env in mid-episode keeps the
