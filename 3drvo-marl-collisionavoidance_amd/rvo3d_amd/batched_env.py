@@ -380,6 +380,24 @@ class BatchedDroneEnv:
                                                 self._stream()), "rvo3d_safety_scan")
         return s
 
+    def building_rows(self, k: int = 4, reach: float = 5.0, below: float = 2.0):
+        """The k nearest buildings of every drone in the current state (rvo3d_building_rows; the rules are in
+        include/rvo3d.h): (rows [E, N, k, 6] float32, b_count [E, N] int32).  A building counts when it passes the
+        reference's gate (rvo_inter.preprocess: roof above p_z - below, centre within reach); a row is
+        [dx, dy, dh, r_b, gap, urg], rounded to two decimals like the observation, rows by ascending gap, zeros from
+        b_count on and in ghost rows.  The env's persistent tensors (one pair per k), overwritten by the next call; one
+        launch, no synchronisation."""
+        k = int(k)
+        cache = self.__dict__.setdefault("_bld_rows", {})
+        if k not in cache and 1 <= k <= 8:
+            cache[k] = (torch.zeros((self.E, self.N, k, 6), dtype=torch.float32, device=self.device),
+                        torch.zeros((self.E, self.N), dtype=torch.int32, device=self.device))
+        rows, cnt = cache.get(k, (None, None))
+        a = _lib.BuildingRowsArgs(k, float(reach), float(below), None if rows is None else rows.data_ptr(), 6 * k, 0,
+                                  None if cnt is None else cnt.data_ptr(), None)
+        _lib.check(_lib.lib().rvo3d_building_rows(self._h, C.byref(a), self._stream()), "rvo3d_building_rows")
+        return rows, cnt
+
     def des_vel(self):
         out = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
         _lib.check(_lib.lib().rvo3d_des_vel(self._h, _ptr(out), self._stream()), "rvo3d_des_vel")
@@ -496,3 +514,96 @@ class BatchedDroneEnv:
         _lib.check(_lib.lib().rvo3d_launch_info(self._h, *[C.byref(x) for x in v]), "launch_info")
         return dict(threads=v[0].value, envs_per_block=v[1].value, blocks=v[2].value,
                     lds_bytes=v[3].value)
+
+
+class BuildingObsEnv(BatchedDroneEnv):
+    """A BatchedDroneEnv whose observation shows the buildings: behind the 12 proprioceptive floats every row carries
+    `building_rows` rows of six floats - the nearest buildings that pass the reference's gate (rvo3d_building_rows,
+    include/rvo3d.h: what ir_gym.observation_reward collects as exter_obs_building and then leaves out) - and then the
+    velocity-obstacle rows as before:
+
+        [ 12 proprio | 6 * k building | 9 * nm VO ]      W = 12 + 6k + 9 * nm, state_dim = 12 + 6k, W_dense = 12 + 9 * nm
+
+    The policy kernels take such a row with state_dim in place of 12 (KernelPolicyStep(state_dim=...); multi_ppo and
+    post_train read env.state_dim).  step / step_policy / observe / observe_envs run what the plain env runs, into a dense
+    pair the env owns (which keeps the plain env's zero-store reuse), then ONE widen launch into `obs` or the caller's
+    obs_out [E, N, W]; reward, done, info, finish and vo_count are the plain env's.  Nothing is allocated after the first
+    call and nothing synchronises.  Behind an auto-resetting step a reset drone's building rows are those of its reset
+    state (velocity 0: urg 0), like its re-observed row."""
+
+    def __init__(self, world, *args, building_rows: int = 4, reach: float = 5.0, below: float = 2.0, **kwargs):
+        k = int(building_rows)
+        if not 1 <= k <= 8:
+            raise ValueError("building_rows must be 1..8")
+        if not (np.isfinite(reach) and reach > 0 and np.isfinite(below) and below >= 0):
+            raise ValueError("reach must be finite and > 0, below finite and >= 0")
+        super().__init__(world, *args, **kwargs)
+        self.building_k, self.reach, self.below = k, float(reach), float(below)
+        self.W_dense = self.W
+        self.state_dim = 12 + 6 * k
+        self.W = self.W_dense + 6 * k
+        self._dense = self.obs  # [E, N, W_dense]: what the step and the observation write; with vo_count the reuse pair
+        self.obs = torch.zeros((self.E, self.N, self.W), dtype=torch.float32, device=self.device)
+        self._dense_scratch = None
+        self._wargs = _lib.BuildingRowsArgs(k, self.reach, self.below, None, self.W, 12, None, self._dense.data_ptr())
+
+    # the pair the library keeps consistent is (dense, vo_count)
+    def _own_versions(self):
+        return (self._dense._version, self.vo_count._version)
+
+    def _touches(self, o, c):
+        po, pc = o.data_ptr() == self._dense.data_ptr(), c.data_ptr() == self.vo_count.data_ptr()
+        return po and pc, po or pc
+
+    def _widen(self, out):
+        """dense + the building rows of the current state -> out [E, N, W] (rvo3d_building_rows, widen mode)."""
+        self._wargs.rows = out.data_ptr()
+        _lib.check(_lib.lib().rvo3d_building_rows(self._h, C.byref(self._wargs), self._stream()), "rvo3d_building_rows")
+        return out
+
+    def step(self, actions, autoreset: bool = False):
+        a, dt = self._actions(actions)
+        self._call_step(a, dt, 0, autoreset, self._dense, self.vo_count,
+                        "rvo3d_step_autoreset" if autoreset else "rvo3d_step")
+        self._widen(self.obs)
+        return self.obs, self.vo_count, self.reward, self.done, self.info, self.finish
+
+    def step_policy(self, a_inc, autoreset: bool = True, obs_out=None, cnt_out=None):
+        a = torch.as_tensor(a_inc, device=self.device).to(torch.float32).contiguous()
+        if tuple(a.shape) != (self.E, self.N, 3):
+            raise AssertionError(f"a_inc must have shape ({self.E}, {self.N}, 3)")
+        o, c = self._outs(obs_out, cnt_out)
+        self._args.acceler = float(self.acceler)
+        self._call_step(a, _lib.RVO3D_F32, 1, autoreset, self._dense, c, "rvo3d_step_policy")
+        self._widen(o)
+        return o, c, self.reward, self.done, self.info, self.finish
+
+    def observe(self, obs_out=None, cnt_out=None):
+        o, c = self._outs(obs_out, cnt_out)
+        own, touches = self._touches(self._dense, c)
+        if touches:
+            self._obs_ver = None
+        _lib.check(_lib.lib().rvo3d_observe(self._h, _ptr(self._dense), _ptr(c), self._stream()), "rvo3d_observe")
+        if own:
+            self._obs_ver = self._own_versions()
+        self._widen(o)
+        return o, c
+
+    def observe_envs(self, env_mask):
+        """observe() for the masked envs.  Every env's row is widened again: the building rows are a function of the
+        state alone, so an env that was not re-observed gets back the floats it had."""
+        m = torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+        if tuple(m.shape) != (self.E,):
+            raise AssertionError(f"env_mask must have shape ({self.E},)")
+        if self._dense_scratch is None:
+            self._dense_scratch = (torch.zeros_like(self._dense), torch.zeros_like(self.vo_count))
+        so, sc = self._dense_scratch
+        keep = self._obs_ver is not None and self._obs_ver == self._own_versions()
+        self._obs_ver = None
+        _lib.check(_lib.lib().rvo3d_observe_envs(self._h, _ptr(m), _ptr(self._dense), _ptr(self.vo_count), _ptr(so),
+                                                 _ptr(sc), self._stream()), "rvo3d_observe_envs")
+        if keep:
+            self._obs_ver = self._own_versions()
+        self._keep = m
+        self._widen(self.obs)
+        return self.obs, self.vo_count

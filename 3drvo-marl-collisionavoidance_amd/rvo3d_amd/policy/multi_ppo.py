@@ -45,7 +45,7 @@ import numpy as np
 import torch
 from torch.optim import Adam
 
-from .policy_step import KernelPolicyStep
+from .policy_step import KernelPolicyStep, check_state_dim
 
 
 def gae_scan(rew, val, cut, gamma=0.99, lam=0.97):
@@ -208,6 +208,7 @@ class multi_ppo:
                  **kwargs):
         np.random.seed(seed)
         self.env, self.ac, self.dist = env, ac_policy, dist
+        check_state_dim(ac_policy, env)  # (a reader for rows of another layout: refused here, not misread later)
         # The agent order of the reference-order update comes from a generator of its own, seeded like
         # the reference's global one (multi_ppo.py:104: np.random.seed(seed); a RandomState(seed) draws
         # the very same sequence): every rank MUST visit the agents in the same order, whatever else in
@@ -440,7 +441,8 @@ class multi_ppo:
             steps, key = ac.setdefault("policy_steps", {}), (mode, E * N)
             kernel_step = steps.get(key)
             if kernel_step is None:
-                kernel_step = steps[key] = KernelPolicyStep(self.ac, mode, env.W, E * N, option=f"rollout mode {mode!r}")
+                kernel_step = steps[key] = KernelPolicyStep(self.ac, mode, env.W, E * N, option=f"rollout mode {mode!r}",
+                                                            state_dim=getattr(env, "state_dim", 12))
             else:
                 kernel_step.clear()  # (a rollout that was interrupted half-way may have left its counters non-zero)
             kernel_step.refresh()  # (once per rollout: the weights do not change inside it)

@@ -35,6 +35,17 @@ def _p(t):
     return C.c_void_p(t.data_ptr())
 
 
+def check_state_dim(ac, env):
+    """An rnn_ac reads the first state_dim floats of a row as the state and the rest as rows of 9; the env says how many
+    state floats its rows hold (BuildingObsEnv.state_dim = 12 + 6k; 12 without the attribute).  A reader made for another
+    number would take building floats for velocity obstacles - silently, where the difference is a multiple of 9."""
+    reader = getattr(getattr(ac, "pi", None), "rnn_reader", None)
+    have, want = getattr(reader, "state_dim", None), int(getattr(env, "state_dim", 12))
+    if have is not None and int(have) != want:
+        raise ValueError(f"the policy's reader was built with state_dim={int(have)}, the env's observation rows hold "
+                         f"state_dim={want} state floats: build rnn_ac(..., state_dim={want})")
+
+
 class KernelPolicyStep:
     """The policy step of `ac` on `rows` observation rows of width `obs_width` as the launches of `kind`.  Owns the
     scratch the launches share - features [rows, width], the list of rows with VO rows [rows], [count, finished
@@ -70,8 +81,11 @@ class KernelPolicyStep:
         """Whether `ac` can run as `kind` on observations of this width (cheap: the models cache what they pack)."""
         return cls.plans(ac, kind, obs_width) is not None
 
-    def __init__(self, ac, kind, obs_width, rows, option="this policy step"):
+    def __init__(self, ac, kind, obs_width, rows, option="this policy step", state_dim=12):
+        """state_dim: the state floats in front of a row's velocity-obstacle rows (12; BuildingObsEnv.state_dim): where
+        the MLP kernels' zero column groups start."""
         self.ac, self.kind, self.obs_width, self.rows, self.option = ac, kind, int(obs_width), int(rows), option
+        self.state_dim = int(state_dim)
         plan, tiles = self.plans(ac, kind, self.obs_width, option)
         self.device = plan["blob"].device
         if kind not in ("mlp", "mlp_x3"):
@@ -110,8 +124,8 @@ class KernelPolicyStep:
         tanh = 1 if plan["tanh"] else 0
         sample = (_p(self.ac.log_std), std_factor, seed, step, _p(act), _p(logp), _p(val))
         # the MLP kernel's input: the observation with the env's counts (column groups of 9 behind the first 12 that are
-        # zero for all rows of a wave are skipped), or the collapsed layer's features
-        x, width, groups = obs, self.obs_width, (_p(cnt), 12, 9)
+        # zero for all rows of a wave are skipped; state_dim in place of 12 for wider rows), or the collapsed layer's features
+        x, width, groups = obs, self.obs_width, (_p(cnt), self.state_dim, 9)
         if listed is not None:
             x, width, groups = self._feat, plan["width"], (None, 0, 0)
             lst, count, done_blocks = _p(self._list), _p(self._count), C.c_void_p(self._count.data_ptr() + 4)

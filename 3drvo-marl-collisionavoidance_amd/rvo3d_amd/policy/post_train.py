@@ -50,7 +50,7 @@ import torch
 
 from .. import _lib
 from ..safety import summarize_safety
-from .policy_step import KernelPolicyStep
+from .policy_step import KernelPolicyStep, check_state_dim
 
 # bits of a record's flag byte (rvo3d_eval_account)
 REC_ARRIVED, REC_FINISHED, REC_COLLIDED, REC_TIMEOUT = 1, 2, 4, 8
@@ -132,6 +132,7 @@ class post_train:
             ac.load_state_dict(ck["model_state"], strict=True)
             policy = ac
         policy.eval()
+        check_state_dim(policy, self.env)
         if self.policy_kernel is not None:
             return self._kernel_policy(policy, std_factor)
 
@@ -146,7 +147,8 @@ class post_train:
         std_factor; noise from (seed, number of calls so far)."""
         env = self.env
         rows = env.E * env.N
-        step = KernelPolicyStep(policy, self.policy_kernel, env.W, rows, option=f"policy_kernel={self.policy_kernel!r}")
+        step = KernelPolicyStep(policy, self.policy_kernel, env.W, rows, option=f"policy_kernel={self.policy_kernel!r}",
+                                state_dim=getattr(env, "state_dim", 12))
         f32 = dict(dtype=torch.float32, device=env.device)
         act, logp, val = torch.empty((rows, 3), **f32), torch.empty(rows, **f32), torch.empty(rows, **f32)  # logp, val: scratch
         calls = [0]

@@ -624,6 +624,55 @@ int rvo3d_eval_account_safety(rvo3d_env *h, const float *reward, const uint8_t *
                               const rvo3d_eval_bufs *bufs, double near_margin,
                               const rvo3d_eval_safety_bufs *sbufs, void *stream);
 
+/* Nearest-building rows of the handle's CURRENT state (positions, velocities, radii): per drone the k buildings with
+ * the smallest gap among those that pass the reference's gate, six floats each - what the reference collects for its
+ * observation (rvo_inter.preprocess, rvo_inter.py:85-107; ir_gym.observation_reward, ir_gym.py:216-219) and then leaves
+ * out of it (:229), with the time to the building's cylinder it defines and never calls (cal_exp_tim_with_building,
+ * rvo_inter.py:248-275).  The buildings are those env e collides with now: its per-env set while sets are attached
+ * (rvo3d_set_env_buildings; unused records hold h = -inf and fail the height gate), else the shared list.  Behind an
+ * auto-resetting step the state of a drone that was reset is its reset state (velocity 0, urg 0): the state its
+ * re-observed row describes.
+ * args: HOST struct of DEVICE pointers.
+ *   Stand-alone mode (obs == NULL): only the columns col0 .. col0 + 6k - 1 of every output row are written, every other
+ *   float of the buffer is left alone.  Needs col0 >= 0 and row_ld >= col0 + 6k.
+ *   Widen mode (obs != NULL; W = 12 + 9 * neighbors_num): the whole wide row [ 12 proprio | 6k building | 9 * nm VO ] -
+ *   columns 0..11 = obs[g][0..11], 12 .. 12 + 6k - 1 the building floats, 12 + 6k .. W + 6k - 1 = obs[g][12 .. W - 1];
+ *   columns behind W + 6k are not written.  Needs col0 == 12 and row_ld >= W + 6k; obs must not overlap rows.  The wide
+ *   row keeps what the policy kernels rely on, with state_dim = 12 + 6k: state floats, vo_count rows of 9, then zeros.
+ * The result is defined by these rules, to the last bit; every value is a float64, every operation rounded on its own (no
+ * FMA), a square is x * x, sqrt and / are correctly rounded, r2(v) = rint(v * 100.0) / 100.0 (np.round(v, 2)).  For a
+ * live drone with position p, velocity v, radius r and the building b = (x_b, y_b, h_b, r_b), in index order:
+ *   1. Gate: ex = p_x - x_b, ey = p_y - y_b, d = sqrt(ex*ex + ey*ey); b passes iff h_b > p_z - below and d <= reach
+ *      (the reference: below = 2, reach = 5).
+ *   2. gap = d - (r + r_b): the term rvo3d_safety_scan minimises for bclear.
+ *   3. t, with R = r + r_b: a = v_x*v_x + v_y*v_y, bq = (2.0*ex)*v_x + (2.0*ey)*v_y, c = (ex*ex + ey*ey) - R*R.
+ *      c <= 0: t = 0.  Else disc = bq*bq - (4.0*a)*c; disc <= 0: t = +inf.  Else s = sqrt(disc), t1 = (-bq + s) / (2.0*a),
+ *      t2 = (-bq - s) / (2.0*a), a root that is not >= 0 counts as +inf, t = t2' < t1' ? t2' : t1'.
+ *      urg = 1.0 / (t + 0.2): the VO rows' input_exp_time (rvo_inter.py:189); 0 for t = +inf, 5 inside the cylinder.
+ *      The time is the reference's, in the plane; column 2 tells whether the roof is below the drone.
+ *   4. Row, each as float32 of r2(.) + 0.0 (no output is -0.0):
+ *        [ r2(x_b - p_x), r2(y_b - p_y), r2(h_b - p_z), r2(r_b), r2(gap), r2(urg) ]
+ *   5. Of the passing buildings the k with the smallest gap are kept, among equal gaps the lower index first, and stored
+ *      by ascending (gap, index).  b_count = min(k, passing); rows from b_count on are zeros.  The key includes the
+ *      index, so the result does not depend on the launch geometry or the tile order.
+ *   6. Ghost rows (counted handle, d >= counts[e]): building floats zeros, b_count 0, in widen mode the whole wide row
+ *      zeros; the ghost's state is not read.
+ * One lane per drone, the buildings through LDS in tiles, the k slots in registers; the geometry of rvo3d_safety_scan.
+ * The rows leave through LDS: consecutive lanes write consecutive floats of a row.  One launch: no allocation, no
+ * synchronisation, no atomics.  Needs a loaded world (RVO3D_ERR_STATE); every argument check (RVO3D_ERR_INVALID) runs
+ * before the first HIP call and a refused call writes nothing. */
+typedef struct rvo3d_building_rows_args {
+  int32_t k;          /* rows per drone, 1..8                                         */
+  double reach;       /* centre-distance gate, finite > 0   (reference: 5.0)          */
+  double below;       /* height gate, finite >= 0           (reference: 2.0)          */
+  float *rows;        /* row g = e*N+d starts at rows + g*row_ld                      */
+  int64_t row_ld;     /* floats per output row                                        */
+  int32_t col0;       /* first column of the 6*k building floats in an output row     */
+  int32_t *b_count;   /* [E][N], nullable: rows written for the drone, 0..k           */
+  const float *obs;   /* nullable: dense observation [E][N][W], W = 12 + 9*nm         */
+} rvo3d_building_rows_args;
+int rvo3d_building_rows(rvo3d_env *h, const rvo3d_building_rows_args *args, void *stream);
+
 /* rvo3d_observe for the envs whose mask byte is non-zero (env_mask [E], required): their rows of obs / vo_count receive
  * bit for bit what rvo3d_observe writes, the other envs' rows are not written at all - an env in mid-episode keeps the
  * observation of its step (ir_gym.observation_reward, with the action), as in the reference, which observes with

@@ -41,6 +41,16 @@ W = env.W
 timed("step + auto-reset (fused, f32 actions)", lambda i: env.step(acts[i % 16], autoreset=True), 719)
 timed("step_policy + auto-reset (trainer glue)", lambda i: env.step_policy(acts[i % 16], autoreset=True), 719)
 timed("observe (env_observation, action 0)", lambda i: env.observe(), 64 + 4 * W + 4 + 24)
+# nearest-building rows (rvo3d_building_rows, k = 4) on this world's state: stand-alone - 6 state doubles in, 24 floats
+# and a count out - and widen mode - the dense row in, the wide row out.  (This world has no buildings: the traffic
+# alone; tools/bench_building_rows.py times both with 50 buildings per env.)
+import ctypes as C
+from rvo3d_amd import _lib
+wide = torch.zeros((E, N, W + 24), device="cuda")
+wargs = _lib.BuildingRowsArgs(4, 5.0, 2.0, wide.data_ptr(), W + 24, 12, None, env.obs.data_ptr())
+timed("building_rows, stand-alone (k = 4)", lambda i: env.building_rows(4), 48 + 96 + 4)
+timed("building_rows, widen mode (k = 4)", lambda i: _lib.check(_lib.lib().rvo3d_building_rows(
+    env._h, C.byref(wargs), env._stream()), "rvo3d_building_rows"), 4 * W + 4 * (W + 24))
 
 
 def manual(i):  # the reference's protocol without the fused auto-reset: step, reset the ended drones, observe again
