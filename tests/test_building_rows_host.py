@@ -165,3 +165,18 @@ def test_argument_table_and_geometry(exe):
     print(res.stderr)
     assert res.returncode == 0, res.stderr[-4000:]
     assert "building rows ok" in res.stdout
+
+
+def test_scenes_of_the_gpu_module():
+    """tests/test_gpu_building_rows.py's host-side helpers: the scene cut down to fleets of one and two, and the 129-record
+    list of the tile-boundary test."""
+    import test_gpu_building_rows as g
+    pos5, vel5, rad5, bld5, _ = g.scene(5, 5, "shared", seed=1)
+    for n in (1, 2, 4):
+        pos, vel, rad, bld, cnt = g.scene_cut(5, n, "shared", seed=1)
+        assert pos.shape == (5, n, 3) and vel.shape == (5, n, 3) and rad.shape == (5, n) and cnt is None
+        assert np.array_equal(pos, pos5[:, :n]) and np.array_equal(vel, vel5[:, :n]) and np.array_equal(bld, bld5)
+    a, b = g.scene_cut(3, 7, "shared", seed=2), g.scene(3, 7, "shared", seed=2)
+    assert all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4]))
+    full = g.boundary_list()
+    assert full.shape == (129, 4) and np.array_equal(full, g.boundary_list()) and np.array_equal(full[:3], bld5[:3])

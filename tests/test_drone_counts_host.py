@@ -184,3 +184,20 @@ def test_update_on_ghost_rows_equals_the_update_without_them(reference_order):
     tr3.update(data)
     tr4.update({k: (v.clone() if torch.is_tensor(v) else v) for k, v in full.items()})
     assert torch.equal(_params(ac3), _params(ac4)) and not torch.equal(_params(ac3), _params(ac))
+
+
+def test_truncated_world_keeps_its_building_counts():
+    """The yardstick helper of tests/test_gpu_drone_counts.py on a world of per-env sets: the listed envs with their
+    first c drones, their own sets and their own set sizes; the per-env scene has an empty and a full set."""
+    from test_gpu_drone_counts import BLD_SCENES, building_scene, truncated
+    world, counts = building_scene(21, 8, True)
+    nb = world.buildings.shape[1]
+    assert counts.tolist() == [21, 1, 3, 5, 2, 8, 7, 21] and world.building_counts[0] == nb and world.building_counts[2] == 0
+    envs = np.array([2, 5, 7])
+    w = truncated(world, envs, 3)
+    assert w.shape == (3, 3, 2) and np.array_equal(w.waypoints, world.waypoints[envs, :3])
+    assert np.array_equal(w.buildings, world.buildings[envs]) and np.array_equal(w.building_counts, world.building_counts[envs])
+    shared, _ = building_scene(21, 8, False)
+    w = truncated(shared, envs, 3)
+    assert w.building_counts is None and np.array_equal(w.buildings, shared.buildings) and len(shared.buildings) == nb
+    assert len(BLD_SCENES) == 6

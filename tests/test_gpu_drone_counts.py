@@ -31,6 +31,37 @@ knife-edge: rows with an oracle margin below 1e-9):
     256 x 3              468 / 4        5343 / 740    0 / 0       - / 740    150 / 150   0 / 1
 
 The tests assert > 0 for VO rows, done and differ in every line, and for resets with autoreset on.
+
+Worlds with buildings (crossing_world has none): synthetic_world(E, N, map, n_points = 2, nb, seed = 41, min_sep = 0.6), the
+buildings one shared list (the xy grid, grid cells that overflow) or a set per env (read through bld_stride /
+bgrid_stride) whose sizes set_sizes() draws: env 0 has all nb, env 2 none.  The same yardstick - plain handles, which
+test_gpu_parity.py pins to the CPU oracle in worlds with buildings -, 25 steps, both autoreset settings:
+
+    N x E      counts                     map            nb   buildings
+    21 x 8     (21, 1, 3, 5, 2, 8, 7)     (12, 12, 5)    3    shared, per-env     L = 32 lanes per env, eight envs a workgroup
+    64 x 6     (64, 33, 48, 1, 63, 2)     (16, 16, 6)    4    per-env             a full wave per env
+    100 x 3    (100, 65, 7)               (20, 20, 8)    6    shared, per-env     two waves
+    256 x 3    (256, 129, 40)             (40, 40, 10)   10   per-env             four waves
+
+What the GPU run tallied (autoreset off / on; "done at a building": live rows whose `done` coincides with bclear <= 0 in
+safety_numpy on the handle's own positions - behind plain steps only, an auto-resetting step has moved the drone away):
+
+    scene                rows with VO   done        done at a building   finish       resets     differ
+    21 x 8 shared        4 / 2          272 / 319   257 / -              1023 / 99    - / 407    0 / 60
+    21 x 8 per-env       4 / 2          210 / 245   193 / -              1023 / 114   - / 350    0 / 115
+    64 x 6 per-env       21 / 8         583 / 603   448 / -              2229 / 251   - / 836    4 / 252
+    100 x 3 shared       15 / 8         437 / 579   376 / -              1373 / 148   - / 715    1 / 130
+    100 x 3 per-env      15 / 7         443 / 461   381 / -              1373 / 155   - / 604    1 / 90
+    256 x 3 per-env      15 / 5         484 / 563   404 / -              796 / 112    - / 675    5 / 242
+
+The CPU oracle, every env run alone at its count, gives the same figures.  The tests assert > 0 for VO rows, done and
+finish in every run, for done at a building behind plain steps, and for resets and differ with autoreset on: these
+drones fly apart from each other, so behind plain steps - where a drone that is `done` stays where it is - a fleet cut
+down to c drones sees what the full fleet sees in all but a few rows, and in none at 21 x 8.
+
+Two more tests at 21 x 8 with per-env sets attach the counts and the sets in either order (rvo3d_set_env_buildings and
+rvo3d_set_drone_counts each rebuild the device's Cold block and carry the other call's fields over), 10 auto-resetting
+steps against the same yardsticks; the second replaces the sets after step 5 (seed 42) on every handle.
 """
 import ctypes as C
 import functools
@@ -40,13 +71,18 @@ import pytest
 import torch
 
 from rvo3d_amd import BatchedDroneEnv, World, _lib
-from rvo3d_amd.worlds import crossing_world
+from rvo3d_amd.safety import safety_numpy
+from rvo3d_amd.worlds import crossing_world, synthetic_world
 
 pytestmark = pytest.mark.gpu
 
 CASES = {(8, 21): (8, 1, 3, 5, 2, 8, 7), (32, 6): (32, 22, 31, 1, 16, 27), (64, 6): (64, 33, 48, 1, 63, 2),
          (100, 3): (100, 65, 7), (256, 3): (256, 129, 40)}
 SMALL = [(8, 21), (64, 6)]
+# worlds with buildings (module docstring): (N, E) -> (counts, map, nb); (N, E, per-env sets)
+BLD_CASES = {(21, 8): ((21, 1, 3, 5, 2, 8, 7), (12.0, 12.0, 5.0), 3), (64, 6): ((64, 33, 48, 1, 63, 2), (16.0, 16.0, 6.0), 4),
+             (100, 3): ((100, 65, 7), (20.0, 20.0, 8.0), 6), (256, 3): ((256, 129, 40), (40.0, 40.0, 10.0), 10)}
+BLD_SCENES = [(21, 8, False), (21, 8, True), (64, 6, True), (100, 3, False), (100, 3, True), (256, 3, True)]
 OUT_KEYS = ("obs", "vo_count", "reward", "done", "info", "finish", "reset_mask")
 STATE_KEYS = ("pos", "vel", "yaw", "pitch", "real_len", "max_dev", "extra_len", "wp_idx", "arrive", "dest")
 STEPS = 25
@@ -73,10 +109,27 @@ def cycled(N, E, cyc=None):
     return np.array([cyc[e % len(cyc)] for e in range(E)], dtype=np.int32)
 
 
+def set_sizes(E, nb, seed=41):
+    """building_counts of a per-env scene: env 0 has all nb buildings, env 2 none, the others a drawn number."""
+    c = np.random.default_rng(seed).integers(0, nb + 1, E).astype(np.int32)
+    c[0], c[2] = nb, 0
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def building_scene(N, E, per_env, seed=41):
+    """synthetic_world with nb buildings - one shared list, or a set per env with set_sizes - and the cycled counts."""
+    cyc, m, nb = BLD_CASES[(N, E)]
+    w = synthetic_world(E, N, m, n_points=2, nb=nb, seed=seed, min_sep=0.6, per_env_buildings=per_env)
+    if per_env:
+        w = World(w.waypoints, w.n_points, w.map_size, w.buildings, set_sizes(E, nb))
+    return w, cycled(N, E, cyc)
+
+
 def truncated(world, envs, c):
-    """The world of the listed envs with their first c drones."""
+    """The world of the listed envs with their first c drones; per-env building sets keep their building_counts."""
     w = world.select(envs)
-    return World(w.waypoints[:, :c].copy(), w.n_points[:, :c].copy(), w.map_size, w.buildings)
+    return World(w.waypoints[:, :c].copy(), w.n_points[:, :c].copy(), w.map_size, w.buildings, w.building_counts)
 
 
 def yardsticks(world, counts, **kw):
@@ -143,7 +196,20 @@ def check_counted(K, Y, counts, keys, what, world=None):
 @functools.lru_cache(maxsize=None)
 def run(N, E, autoreset, env_train=True):
     """The comparison of the module docstring; returns the tallies the tests assert on."""
-    world, counts = scene(N, E), cycled(N, E)
+    return run_world(scene(N, E), cycled(N, E), autoreset, env_train)
+
+
+@functools.lru_cache(maxsize=None)
+def run_buildings(N, E, per_env, autoreset):
+    return run_world(*building_scene(N, E, per_env), autoreset)
+
+
+def run_world(world, counts, autoreset, env_train=True):
+    """run() on any world.  With buildings the tally `bdone` counts the live rows whose `done` coincides with
+    bclear <= 0 in safety_numpy on the handle's own positions - behind plain steps only: an auto-resetting step has
+    moved every `done` drone to its start before anybody can look."""
+    N, E = world.shape[1], world.shape[0]
+    has_bld = np.size(world.buildings) > 0
     K = BatchedDroneEnv(world.with_drone_counts(counts), env_train=env_train, reuse_obs=False)
     F = BatchedDroneEnv(world, env_train=env_train)
     Y = yardsticks(world, counts, env_train=env_train)
@@ -153,7 +219,7 @@ def run(N, E, autoreset, env_train=True):
     for x in [K, F] + [y for _, y in Y.values()]:
         x.observe()
     check_counted(K, Y, counts, ("obs", "vo_count"), "observe", world)
-    tally = dict(vo=0, done=0, finish=0, resets=0, differ=0)
+    tally = dict(vo=0, done=0, bdone=0, finish=0, resets=0, differ=0)
     part = np.arange(N)[None, :] < np.where(counts < N, counts, 0)[:, None]   # live rows of the envs with c < N
     for t in range(STEPS):
         acts = [(K, follow_counted(K)), (F, follow(F))] + [(y, follow(y)) for _, y in Y.values()]
@@ -167,6 +233,10 @@ def run(N, E, autoreset, env_train=True):
         tally["finish"] += int(np.sum(got["finish"][live] != 0))
         if autoreset:
             tally["resets"] += int(np.sum(got["reset_mask"][live] != 0))
+        elif has_bld:
+            bclear = safety_numpy(got["pos"], 0.2, world.map_size, 0.5, counts=counts, buildings=world.buildings,
+                                  building_counts=world.building_counts)[1]
+            tally["bdone"] += int(np.sum((got["done"][live] != 0) & (bclear[live] <= 0)))
         tally["differ"] += int(np.sum(np.any(got["obs"] != host(F.obs), axis=-1) & part))
     # the error word: what the yardsticks raised between them (env_train off: the reference's math domain error)
     want = 0
@@ -186,6 +256,87 @@ def test_counted_envs_equal_plain_handles_of_their_size(N, E, autoreset):
     assert tally["vo"] > 0 and tally["done"] > 0 and tally["differ"] > 0, tally
     if autoreset:
         assert tally["resets"] > 0, tally
+
+
+@pytest.mark.parametrize("autoreset", [False, True])
+@pytest.mark.parametrize("N,E,per_env", BLD_SCENES)
+def test_counted_envs_in_worlds_with_buildings(N, E, per_env, autoreset):
+    """env_kernel_counted along the building path: the shared list with its xy grid, and per-env sets read through
+    bld_stride / bgrid_stride, one of them empty and one full."""
+    world, counts = building_scene(N, E, per_env)
+    if per_env:
+        assert world.per_env_buildings and 0 in world.building_counts and world.buildings.shape[1] in world.building_counts
+    tally = run_buildings(N, E, per_env, autoreset)
+    print(f"{N} x {E}, {'per-env sets' if per_env else 'shared list'}, autoreset {autoreset}: {tally}")
+    assert tally["vo"] > 0 and tally["done"] > 0 and tally["finish"] > 0, tally
+    if autoreset:
+        assert tally["resets"] > 0 and tally["differ"] > 0, tally
+    else:   # (plain steps: the drones of these scenes stay apart, 21 x 8 has no row that differs - module docstring)
+        assert tally["bdone"] > 0, tally
+
+
+def other_sets(E, N, seed=42):
+    """Per-env sets for the 21 x 8 scene from another seed, with the scene's set sizes."""
+    _, m, nb = BLD_CASES[(N, E)]
+    return synthetic_world(E, 1, m, nb=nb, seed=seed, per_env_buildings=True).buildings
+
+
+def ordering_run(K, world, counts, swap_at=None):
+    """10 auto-resetting steps of the counted handle K against the yardsticks of `world`, beside K0, a counted handle
+    that never had a building (and, from swap_at on, beside K1, a counted handle that keeps the first sets while K and
+    the yardsticks get other_sets).  Returns the rows whose `done` differs from K0's, and at step swap_at from K1's."""
+    N, E = world.shape[1], world.shape[0]
+    Y = yardsticks(world, counts)
+    K0 = BatchedDroneEnv(World(world.waypoints, world.n_points, world.map_size).with_drone_counts(counts))
+    K1 = BatchedDroneEnv(world.with_drone_counts(counts)) if swap_at is not None else None
+    assert "env_kernel_counted" in K.kernel_name()
+    handles = [K, K0] + ([K1] if K1 else []) + [y for _, y in Y.values()]
+    poison(K)
+    for x in handles:
+        x.observe()
+    check_counted(K, Y, counts, ("obs", "vo_count"), "observe", world)
+    live = np.arange(N)[None, :] < counts[:, None]
+    built = swapped = 0
+    for t in range(10):
+        if t == swap_at:
+            new = other_sets(E, N)
+            K.set_env_buildings(new, world.building_counts)
+            for envs, y in Y.values():
+                y.set_env_buildings(new[envs], world.building_counts[envs])
+        acts = [(x, follow_counted(x) if x.drone_counts is not None else follow(x)) for x in handles]
+        poison(K)
+        for x, a in acts:
+            x.step(a, autoreset=True)
+        got = check_counted(K, Y, counts, OUT_KEYS, f"step {t}", world)
+        built += int(np.sum((got["done"] != host(K0.done))[live]))
+        if t == swap_at:
+            swapped = int(np.sum((got["done"] != host(K1.done))[live]))
+    assert K.error_flags() == 0
+    for x in handles:
+        x.close()
+    return built, swapped
+
+
+def test_counts_first_then_env_buildings():
+    """rvo3d_set_env_buildings on a counted handle: the Cold block it rebuilds keeps the counts."""
+    world, counts = building_scene(21, 8, True)
+    K = BatchedDroneEnv(World(world.waypoints, world.n_points, world.map_size).with_drone_counts(counts), reuse_obs=False)
+    K.set_env_buildings(world.buildings, world.building_counts)
+    built, _ = ordering_run(K, world, counts)
+    print(f"counts first: rows whose done differs from a handle without buildings {built}")
+    assert built > 0
+
+
+def test_env_buildings_first_then_counts():
+    """rvo3d_set_drone_counts on a handle of per-env sets: the Cold block it rebuilds keeps the sets; new sets after
+    step 5 show in the very next step."""
+    world, counts = building_scene(21, 8, True)
+    K = BatchedDroneEnv(world, reuse_obs=False)
+    K.set_drone_counts(counts)
+    built, swapped = ordering_run(K, world, counts, swap_at=5)
+    print(f"buildings first: rows whose done differs from a handle without buildings {built}, "
+          f"from a handle that kept the old sets at the step behind the swap {swapped}")
+    assert built > 0 and swapped > 0
 
 
 @pytest.mark.parametrize("autoreset", [False, True])

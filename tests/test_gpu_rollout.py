@@ -4,7 +4,10 @@ and the buffer stores in one pass) and rvo3d_rollout_account (reward slot, episo
 cuts), each against a plain PyTorch float32 statement of the same lines - these are floating-point
 kernels: tolerance 1e-5 on mu / v, 1e-4 on log-probabilities (fast log / exp), stated per check -
 and the fused rollout loop as a whole: replaying the stored actions through a second env must
-reproduce every stored observation bit for bit."""
+reproduce every stored observation bit for bit.
+The MLP kernels' zero-column-group skipping also runs at every state_dim a BuildingObsEnv row can have (12 + 6k,
+k = 1..8; neighbors_num 3 and 10: W = 45 .. 87 and 108 .. 126, the widths beyond 126 fit no kernel instantiation), both
+entry points: test_mlp_kernels_at_every_state_dim_of_the_wide_env."""
 import ctypes as C
 import math
 
@@ -256,6 +259,75 @@ def test_policy_mlp_sample_skips_zero_column_groups_exactly(nm):
     L = _lib.lib()
     assert L.rvo3d_policy_mlp_sample(_p(blob), W, _p(x), W, rows, _p(cnt), W + 1, 9, 1, _p(log_std), 1.0, 0, 0,
                                      _p(dense[0]), _p(dense[1]), _p(dense[2]), None, None, None) == -1
+
+
+def wide_rows(k, nm, rows, seed):
+    """Rows shaped like BuildingObsEnv's: state_dim = 12 + 6k random state floats, 9 per kept VO row, zeros behind, with
+    the count mixtures of the test above inside the 32-row groups.  -> (x [rows, W], cnt [rows] int32, state_dim, W)"""
+    sd, W = 12 + 6 * k, 12 + 6 * k + 9 * nm
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    cnt = torch.randint(0, 3, (rows,), device=DEV, generator=g, dtype=torch.int32)           # sparse groups
+    cnt[torch.rand(rows, device=DEV, generator=g) < 0.02] = nm                                  # a dense row among them
+    cnt[64:128] = torch.randint(0, nm + 1, (64,), device=DEV, generator=g, dtype=torch.int32)   # mixed groups
+    cnt[128:192] = nm                                                                           # all-dense groups
+    cnt[192:256] = 0                                                                            # all-empty groups
+    x = torch.randn((rows, W), device=DEV, generator=g)
+    x *= (torch.arange(W, device=DEV)[None, :] < (sd + 9 * cnt.long())[:, None]).float()
+    return x, cnt, sd, W
+
+
+@pytest.mark.parametrize("nm", [3, 10])
+@pytest.mark.parametrize("entry", ["rvo3d_policy_mlp_sample", "rvo3d_policy_mlp_x3_sample"])
+def test_mlp_kernels_at_every_state_dim_of_the_wide_env(entry, nm):
+    """state_dim = 12 + 6k for k = 1..8 in place of 12: the zero column groups start at state_dim + 9 * vo_count, and every
+    k moves them against the 16-column steps.  With (cnt, state_dim, 9) the kernel returns the bits of the call without
+    counts, and both agree with the kernel's arithmetic restated in PyTorch: the bf16 kernel with _mlp_emulation within
+    1e-2 on mu and v (the bound of the test above), the x3 kernel with the float64 forward within the bounds of
+    test_gpu_policy_x3.py (mu before the tanh: max 1e-4, mean 1e-5; v: 1e-4 relative to max(1, |v|)).  Widths no kernel
+    instantiation takes (KernelPolicyStep.fits) are left out and printed."""
+    from rvo3d_amd.policy.policy_step import KernelPolicyStep
+    from test_policy_x3_host import MU_MAX, MU_MEAN, V_REL, forward64
+    x3 = entry.endswith("x3_sample")
+    fn = getattr(_lib.lib(), entry)
+    rows = 64 * 5 + 17
+    log_std = torch.tensor([-1.0, -0.5, -1.5], device=DEV)
+    ran, left_out = [], []
+    for k in range(1, 9):
+        x, cnt, sd, W = wide_rows(k, nm, rows, seed=100 * k + nm)
+        torch.manual_seed(W)
+        ac = mlp_ac(W).to(DEV)
+        if not KernelPolicyStep.fits(ac, "mlp_x3" if x3 else "mlp", W):
+            left_out.append((k, nm, W))
+            continue
+        blob = ac.mlp_blob("x3" if x3 else "bf16")["blob"]
+        tanh = 0 if x3 else 1
+
+        def run(counts, state_dim):
+            out = [torch.full(s, 9.0, device=DEV) for s in ((rows, 3), (rows,), (rows,), (rows, 3), (rows, 3))]
+            rc = fn(_p(blob), W, _p(x), W, rows, _p(counts), state_dim, 9, tanh, _p(log_std), 1.0, 7, 0,
+                    *[_p(t) for t in out], C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            torch.cuda.synchronize()
+            return rc, out   # act, logp, val, mu, raw
+        rc_d, dense = run(None, 0)
+        rc_s, sparse = run(cnt, sd)
+        assert rc_d == 0 and rc_s == 0, (k, rc_d, rc_s)
+        for a, b, name in zip(dense, sparse, ("act", "logp", "val", "mu", "raw")):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (k, name, int((a != b).sum()))
+        assert bool((cnt == 0).any()) and bool((cnt == nm).any()) and bool(x[:, 12:sd].any())
+        if x3:
+            with torch.no_grad():
+                z64, v64 = forward64(ac.pi_net, x), forward64(ac.v_net, x).squeeze(-1)
+            d_mu, d_v = (sparse[3].double() - z64).abs(), (sparse[2].double() - v64).abs()
+            assert float(d_mu.max()) <= MU_MAX and float(d_mu.mean()) <= MU_MEAN, (k, float(d_mu.max()), float(d_mu.mean()))
+            assert bool((d_v <= V_REL * v64.abs().clamp(min=1.0)).all()), (k, float(d_v.max()))
+        else:
+            z_emu, v_emu = _mlp_emulation(ac, x)
+            d_mu, d_v = (sparse[3] - torch.tanh(z_emu)).abs(), (sparse[2] - v_emu).abs()
+            assert float(d_mu.max()) < 1e-2 and float(d_v.max()) < 1e-2, (k, float(d_mu.max()), float(d_v.max()))
+        assert run(cnt, W + 1)[0] == -1, k                          # more state floats than the row has
+        ran.append(k)
+    print(f"{entry}, nm {nm}: ran k = {ran}; left out (k, nm, W): {left_out}")
+    assert ran and all(W > 126 for _, _, W in left_out)
 
 
 def test_policy_mlp_sample_reads_only_the_callers_bytes_and_rejects_bad_arguments():

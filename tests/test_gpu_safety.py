@@ -1,7 +1,8 @@
 """Safety metrics on the device (include/rvo3d.h: rvo3d_safety_scan, rvo3d_eval_account_safety): the scan against its numpy
 restatement (rvo3d_amd.safety.safety_numpy) bit for bit over every launch geometry and building set-up, its argument
 contract, counted handles, the three predicates against the step's own `done`, and the episode records of the fused
-evaluation loop."""
+evaluation loop.  The shapes and what each is there for stand next to SHAPES; the counted scans (counted_scan) run at
+(4, 130) with per-env building sets and at (70, 4), shared list and per-env sets."""
 import ctypes as C
 
 import numpy as np
@@ -17,8 +18,10 @@ pytestmark = pytest.mark.gpu
 MAP = (20.0, 16.0, 8.0)
 INF = np.inf
 # (E, N): a sole drone, packed envs, more envs than one workgroup packs (64 at 4 lanes per env), every ring width, more
-# than one wave per env
-SHAPES = [(5, 1), (3, 2), (70, 4), (7, 33), (4, 64), (3, 65), (2, 130), (2, 257)]
+# than one wave per env, and the widest workgroup (N = 512: eight waves feed the LDS fold over waves).
+# Counted handles run at (4, 130) - counts 130, 65, 64, 1: waves of ghosts alone in the fold, a wave with one live lane, an
+# env of a single drone, with per-env building sets - and packed at (70, 4) with counts cycling 4, 1, 3, 2.
+SHAPES = [(5, 1), (3, 2), (70, 4), (7, 33), (4, 64), (3, 65), (2, 130), (2, 257), (1, 512)]
 
 
 def bits(a):
@@ -43,6 +46,10 @@ def planted_state(E, N, seed):
     pos[E - 1, N - 1] = [9.0, 9.0, 2.0]
     if N >= 2:
         pos[E - 1, N - 2] = [9.5, 9.0, np.nextafter(2.0, INF)]
+        # a crowded env (512 drones): a random drone that touches the planted pair would hide its sep == 0; it goes 3 m up
+        for j in range(2, N):
+            if min(np.linalg.norm(pos[0, j] - pos[0, i]) - (rad[0, j] + 0.25) for i in (0, 1)) <= 0.0:
+                pos[0, j, 2] += 3.0
     return pos, rad
 
 
@@ -193,6 +200,47 @@ def test_counted_handles_equal_plain_handles():
         assert np.array_equal(bits(again[i]), bits(want[i])), i
     assert np.array_equal(again[3], want[3])
     env.close()
+
+
+def counted_scan(E, N, counts, kind):
+    """planted_state on a counted handle with NaN in the ghosts' state against safety_numpy(counts=, building_counts=):
+    live rows bit for bit, ghost rows +inf, near_pairs equal, and each of the three predicates true in some live row.
+    The planted drones a count would cut away stand inside the live range: the last env's drone at z = 2.0 is its
+    drone 0, the one at nextafter(2.0) the last live drone of env 1; drone 0 of env 2 stands inside the planted building."""
+    counts = np.array(counts, dtype=np.int32)
+    live = np.arange(N)[None, :] < counts[:, None]
+    pos, rad = planted_state(E, N, seed=E * 1000 + N + 1)
+    assert counts[0] >= 4 and counts[E - 1] == 1
+    pos[E - 1, 0] = [9.0, 9.0, 2.0]
+    pos[1, counts[1] - 1] = [9.5, 9.0, np.nextafter(2.0, INF)]
+    pos[2, 0] = [9.0, 10.25, 1.5]
+    pos[~live] = np.nan
+    bld, cnt = buildings_for(kind, E, seed=N)
+    env = make_env(E, N, bld, cnt, rad, drone_counts=counts)
+    env.set_state(pos=pos)
+    got = [t.cpu().numpy() for t in env.safety(0.5)]
+    env.close()
+    want = safety_numpy(pos, rad, MAP, 0.5, counts=counts, buildings=bld, building_counts=cnt)
+    for name, g, w in zip(("sep", "bclear", "wall"), got, want):
+        bad = np.argwhere(bits(g) != bits(w))
+        assert bad.size == 0, (kind, name, len(bad), bad[:4].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
+        assert np.isposinf(g[~live]).all(), (kind, name)
+    assert got[3].dtype == np.int32 and np.array_equal(got[3], want[3]), (kind, got[3], want[3])
+    assert np.isposinf(got[0][E - 1, 0]) and got[3][E - 1] == 0          # the env of one drone
+    assert np.isfinite(got[0][live & (counts[:, None] > 1)]).all() and np.isfinite(got[2][live]).all()
+    assert got[1][E - 1, 0] <= 0.5                                       # the planted building counts at p_z == h
+    fired = [int((got[0][live] <= 0).sum()), int((got[1][live] <= 0).sum()), int((got[2][live] < 0).sum())]
+    print(f"({E}, {N}) {kind}: live rows {int(live.sum())}, fired: pairs, buildings, walls {fired}, near {got[3].sum()}")
+    assert min(fired) > 0 and got[3].sum() > 0
+
+
+def test_counted_scan_of_several_waves_with_per_env_sets():
+    counted_scan(4, 130, (130, 65, 64, 1), "per_env")
+
+
+@pytest.mark.parametrize("kind", ["shared", "per_env"])
+def test_counted_scan_in_the_packed_geometry(kind):
+    counted_scan(70, 4, [(4, 1, 3, 2)[e % 4] for e in range(70)], kind)
 
 
 def test_predicates_equal_the_steps_done():
