@@ -627,6 +627,26 @@ int rvo3d_set_env_buildings(rvo3d_env* h, const double* buildings, const int32_t
   RVO3D_API_END
 }
 
+int rvo3d_move_env_buildings(rvo3d_env* h, const rvo3d_building_motion* m, double dt, const uint8_t* env_mask,
+                             double* buildings_out, void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  std::string err;
+  if (int rc = rvo3d::check_move_env_buildings(h->world_loaded, h->env_bld != nullptr, m, dt, err)) return fail(rc, err);
+  DeviceGuard dg;
+  if (int rc = dg.enter(h->cfg.device)) return rc;
+  const rvo3d::Cold& C = h->live;  // the sets': records and cells inside the handle's env_bld allocation
+  if (C.nb == 0) return RVO3D_OK;
+  const rvo3d::MotionArgs A{const_cast<double*>(C.bld), const_cast<uint16_t*>(C.bgrid), C.bld_stride, C.bgrid_stride,
+                            C.nb, C.bgx, C.bgy, C.bg_inv, h->rmax, dt, m->ends, m->speed, m->leg, env_mask, buildings_out};
+  hipLaunchKernelGGL(rvo3d::move_buildings_kernel, dim3((unsigned)h->P.E), dim3(rvo3d::kMotionThreads), 0,
+                     static_cast<hipStream_t>(stream), A);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
 int rvo3d_set_drone_counts(rvo3d_env* h, const int32_t* counts, void* stream) {
   RVO3D_API_BEGIN
   // every argument check, and all of the host's work, before the first HIP call

@@ -367,6 +367,33 @@ inline int check_env_buildings(int E, const double* buildings, const int32_t* co
   return RVO3D_OK;
 }
 
+// The argument checks of rvo3d_move_env_buildings (its rvo3d_building_motion holds device pointers: what they point at
+// is the kernel's to read).  sets_attached: rvo3d_set_env_buildings is in force on the handle.
+inline int check_move_env_buildings(bool world_loaded, bool sets_attached, const rvo3d_building_motion* m, double dt,
+                                    std::string& err) {
+  if (!world_loaded) {
+    err = "rvo3d_load_world has not been called";
+    return RVO3D_ERR_STATE;
+  }
+  if (!sets_attached) {
+    err = "no per-env building sets are attached (rvo3d_set_env_buildings)";
+    return RVO3D_ERR_STATE;
+  }
+  if (!m) {
+    err = "null rvo3d_building_motion";
+    return RVO3D_ERR_INVALID;
+  }
+  if (!m->ends || !m->speed || !m->leg) {
+    err = "ends, speed and leg are required";
+    return RVO3D_ERR_INVALID;
+  }
+  if (!std::isfinite(dt) || !(dt >= 0.0)) {
+    err = "dt must be finite and >= 0";
+    return RVO3D_ERR_INVALID;
+  }
+  return RVO3D_OK;
+}
+
 // The checks rvo3d_sample_routes_city and rvo3d_plan_routes make of their rvo3d_city (its pointers are device
 // pointers: what they point at is the kernels' to bound).
 inline int check_city(const rvo3d_city* c, std::string& err) {

@@ -13,9 +13,10 @@ from ._lib import build_hip, lib, lib_path, RVO3DError  # noqa: F401
 from .batched_env import BatchedDroneEnv, BuildingObsEnv  # noqa: F401
 from .worlds import (World, crossing_world, load_world_dir, stack_worlds, synthetic_world,  # noqa: F401
                      synthetic_actions)
+from .building_motion import BuildingMotion, synthetic_patrols  # noqa: F401
 from .routes import CityRoutePlanner, RouteSampler  # noqa: F401
 from .safety import safety_numpy, summarize_safety  # noqa: F401
 from . import sharding  # noqa: F401
 
-__all__ = ["BatchedDroneEnv", "BuildingObsEnv", "CityRoutePlanner", "RouteSampler", "World", "crossing_world", "load_world_dir", "stack_worlds", "synthetic_world",
+__all__ = ["BatchedDroneEnv", "BuildingMotion", "BuildingObsEnv", "CityRoutePlanner", "synthetic_patrols", "RouteSampler", "World", "crossing_world", "load_world_dir", "stack_worlds", "synthetic_world",
            "synthetic_actions", "safety_numpy", "summarize_safety", "build_hip", "lib", "lib_path", "RVO3DError"]

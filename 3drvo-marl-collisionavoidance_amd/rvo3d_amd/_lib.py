@@ -118,6 +118,11 @@ class BuildingRowsArgs(C.Structure):
                 ("row_ld", C.c_int64), ("col0", C.c_int32), ("b_count", C.c_void_p), ("obs", C.c_void_p)]
 
 
+class BuildingMotionArgs(C.Structure):
+    """rvo3d_building_motion (rvo3d_move_env_buildings)."""
+    _fields_ = [("ends", C.c_void_p), ("speed", C.c_void_p), ("leg", C.c_void_p)]
+
+
 class StateView(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("px", "py", "pz", "vx", "vy", "vz", "yaw", "pitch", "real_len", "max_dev",
@@ -125,7 +130,8 @@ class StateView(C.Structure):
 
 
 # every symbol include/rvo3d.h declares (tests check the library exports them all)
-SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_buildings", "rvo3d_set_drone_counts",
+SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_buildings", "rvo3d_move_env_buildings",
+           "rvo3d_set_drone_counts",
            "rvo3d_drone_counts", "rvo3d_rollout_account_n", "rvo3d_set_routes",
            "rvo3d_get_routes", "rvo3d_sample_routes", "rvo3d_sample_routes_city", "rvo3d_plan_routes", "rvo3d_reset",
            "rvo3d_reset_drones", "rvo3d_observe", "rvo3d_step", "rvo3d_step_autoreset",
@@ -164,6 +170,7 @@ def lib():
     L.rvo3d_destroy.argtypes = [vp]
     L.rvo3d_load_world.argtypes = [vp] * 7
     L.rvo3d_set_env_buildings.argtypes = [vp, vp, vp, i32, vp]
+    L.rvo3d_move_env_buildings.argtypes = [vp, C.POINTER(BuildingMotionArgs), C.c_double, vp, vp, vp]
     L.rvo3d_set_drone_counts.argtypes = [vp, vp, vp]
     L.rvo3d_drone_counts.argtypes = [vp, C.POINTER(vp)]
     L.rvo3d_set_routes.argtypes = [vp, vp, vp, vp, vp]

@@ -57,6 +57,7 @@ class BatchedDroneEnv:
         self._h = h
         self._env_bld = None  # the last set_env_buildings: (buildings, counts) host arrays, None: the world's shared list
         self._dev_bld = None  # device_buildings()' cache
+        self._motion = None   # attach_building_motion: advanced in front of every step
         wp = np.ascontiguousarray(world.waypoints, dtype=np.float64)
         npts = np.ascontiguousarray(world.n_points, dtype=np.int32)
         bld = np.zeros((0, 4)) if per_env else np.ascontiguousarray(world.buildings, dtype=np.float64)
@@ -117,7 +118,13 @@ class BatchedDroneEnv:
         """A building set per env from the next step on (rvo3d_set_env_buildings): buildings [E, nb_max, 4] = x,y,h,r,
         counts [E] (env e collides with buildings[e, :counts[e]]; None: all nb_max).  Replaces the sets in force, e.g.
         to re-draw the cities between epochs; set_env_buildings(None) goes back to the world's shared list.
-        Synchronises the current stream."""
+        Synchronises the current stream.  Detaches a building motion (attach_building_motion)."""
+        self._upload_env_buildings(buildings, counts)
+        if self._motion is not None:
+            self._motion._unbind()
+            self._motion = None
+
+    def _upload_env_buildings(self, buildings, counts=None):
         b = c = None
         nb_max = 0
         if buildings is not None:
@@ -186,7 +193,11 @@ class BatchedDroneEnv:
     def device_buildings(self):
         """What the env collides with now, as device tensors: (buildings [1, nb, 4] - the world's shared list - or
         [E, nb_max, 4] - the sets of the last set_env_buildings - float64, counts [E] int32 or None).  Built on first
-        use and kept until the next set_env_buildings; CityRoutePlanner.redraw reads the city from here."""
+        use and kept until the next set_env_buildings; CityRoutePlanner.redraw reads the city from here.  With a building
+        motion attached: the live tensor the motion's launches keep up to date (where the buildings are now) and the
+        counts."""
+        if self._motion is not None:
+            return self._motion.buildings, self._motion._counts
         if self._dev_bld is None:
             if self._env_bld is not None:
                 b, c = self._env_bld
@@ -196,6 +207,31 @@ class BatchedDroneEnv:
             self._dev_bld = (torch.from_numpy(np.ascontiguousarray(b)).to(self.device),
                              None if c is None else torch.from_numpy(c).to(self.device))
         return self._dev_bld
+
+    def attach_building_motion(self, motion):
+        """Moving buildings (rvo3d_amd.building_motion.BuildingMotion; None detaches): from the next step on every step -
+        step, step_policy, the trainer's and the evaluator's - first advances the records of the per-env sets by one
+        time step (one more launch: rvo3d_move_env_buildings), then steps the drones, which are tested against the
+        buildings where they are now; safety(), building_rows() and device_buildings() see them there as well.  Needs
+        per-env sets in force and a motion of their shape [E, nb_max]; set_env_buildings detaches it.  The records stay
+        where the motion left them when it is detached."""
+        if motion is None:
+            if self._motion is not None:
+                # the host copy of the sets follows the buildings: what device_buildings() reports from now on
+                self._env_bld = (self._motion.buildings.cpu().numpy(), self._env_bld[1])
+                self._dev_bld = None
+                self._motion._unbind()
+                self._motion = None
+            return
+        if self._env_bld is None:
+            raise ValueError("attach_building_motion needs per-env building sets (set_env_buildings)")
+        if self._motion is not None and self._motion is not motion:
+            self.attach_building_motion(None)
+        b, c = self._env_bld
+        if motion.shape != tuple(b.shape[:2]):
+            raise ValueError(f"the motion is for [E, nb_max] = {motion.shape}, the sets in force have {tuple(b.shape[:2])}")
+        motion._bind(self, b, c)
+        self._motion = motion
 
     def set_routes(self, waypoints, n_points=None, env_mask=None):
         """New routes from the next call on (rvo3d_set_routes): waypoints [E, N, P, 3] float64, n_points [E, N] int32
@@ -270,6 +306,8 @@ class BatchedDroneEnv:
         args.prev_vo_count = c.data_ptr() if reuse else None
         if touches:
             self._obs_ver = None
+        if self._motion is not None:
+            self._motion.advance()  # the buildings move before the drones of the same step
         _lib.check(_lib.lib().rvo3d_step_ex(self._h, C.byref(args), self._stream()), name)
         if own:
             self._obs_ver = self._own_versions()

@@ -258,6 +258,7 @@ class multi_ppo:
         # graphs do not (they hold the plan's LayerNorm sums by value): the rollout after an update() captures them
         # again.  A parameter that moved to another storage drops the graphs of either mode.
         self.graph_rollout = bool(graph_rollout)
+        self._refuse_graph_with_motion()
         # the rollout's policy GEMMs ([E*N, 128] x [128, 512], [E*N, 256] x [256, 256], bf16) through PyTorch's
         # TunableOp: the first call of a shape times hipBLASLt's candidate kernels (<= 3 s per shape) and keeps
         # the fastest - at 64 x 4096 a 256x256x64 stream-K kernel, 70 us, instead of the heuristic's 84 us
@@ -405,6 +406,13 @@ class multi_ppo:
             finally:
                 tun.enable(was)
         return ctx()
+
+    def _refuse_graph_with_motion(self):
+        """Moving buildings (BatchedDroneEnv.attach_building_motion) add a launch in front of every env step that the
+        captured graphs do not hold: graph_rollout=True refuses such an env (the stream path trains on it)."""
+        if self.graph_rollout and getattr(self.env, "_motion", None) is not None:
+            raise ValueError("graph_rollout=True does not replay the launch of an attached building motion: "
+                             "use graph_rollout=False")
 
     def _collect_fused(self, final_reset=True):
         """collect() with the per-step glue on the device: per step the policy part - the launches of a KernelPolicyStep
@@ -594,6 +602,7 @@ class multi_ppo:
         under ONE autocast region (weight casts are cached across the steps).
         final_reset=False (rollout_profile only) leaves out the epoch-end full reset."""
         self._counts_ptr()  # (refuses drone counts the trainer has not been told about: set_live())
+        self._refuse_graph_with_motion()  # (a motion attached after the trainer was built)
         if self._fused_ok():
             return self._collect_fused(final_reset)
         env, buf = self.env, self.buf

@@ -109,6 +109,40 @@ int rvo3d_load_world(rvo3d_env *h, const double *waypoints, const int32_t *n_poi
  * before the first HIP call; a refused call leaves the handle as it was. */
 int rvo3d_set_env_buildings(rvo3d_env *h, const double *buildings, const int32_t *counts, int32_t nb_max, void *stream);
 
+/* Moving buildings: advances the records of the attached per-env sets by one time step on the device and rebuilds the
+ * per-cell lists where they are - the reference's parked dynamic obstacle (obs_circle: cal_des_vel_omni, full speed
+ * towards the goal; move_forward, state += vel * step_time; motion_model.motion_omni), patrolling between two endpoints
+ * where the reference's stops at its goal.  m: HOST struct of DEVICE pointers the caller owns, nb_max that of the attached
+ * sets; env_mask [E] DEVICE bytes (NULL = every env); buildings_out [E][nb_max][4] DEVICE, nullable.
+ * The result is defined by these rules, to the last bit; every value is a float64, every operation rounded on its own (no
+ * FMA), a square is x * x, sqrt and / are correctly rounded.  For env e with a non-zero mask byte and its record
+ * b = (x, y, h, r), with s = speed[e][b], k = leg[e][b] & 1 and T = ends[e][b][k]:
+ *   1. h == -inf (the filler behind counts[e]): nothing else of the record is read, it is not moved, not listed and not
+ *      written to buildings_out.
+ *   2. step = s * dt.  !(step > 0) - speed 0, a NaN speed, dt 0: the record and leg[e][b] keep their bits (a static
+ *      building; its ends are not read).
+ *   3. Else dx = T_x - x, dy = T_y - y, d = sqrt(dx*dx + dy*dy).  d <= step: (x, y) = T exactly and leg[e][b] ^= 1; the rest
+ *      of the step is not spent.  Else x = x + (dx / d) * step, y = y + (dy / d) * step.  h and r never change.
+ *   4. buildings_out[e][b] = the record's four doubles after the move, for every live record (static ones included).
+ *   5. Every cell of env e's lists then holds what rvo3d_set_env_buildings computes for the live records where they are
+ *      now: the cell widened by 1e-3 m and unbounded at the map's edge, a building listed within min(largest drone
+ *      radius + r_b, 5) + 1e-3 of it, in index order, count 0xffff once more than 15 are listed.
+ * So a handle whose sets were moved here behaves bit for bit as a handle that was given the same positions through
+ * rvo3d_set_env_buildings.  Buildings move before the drones of the same step: call this, then the step, and the step
+ * tests the post-move drones against the post-move buildings.  A building may leave the map (the edge cells are
+ * unbounded).  Finite ends are the caller's duty.  A later rvo3d_set_env_buildings replaces the records and leaves the
+ * caller's leg alone.  Nothing of an env whose mask byte is zero is read or written.
+ * One launch, one workgroup per env: no allocation, no synchronisation, no atomics.  RVO3D_ERR_STATE without a loaded
+ * world or without attached sets; RVO3D_ERR_INVALID for a null m or a null pointer inside it, and for dt not finite or
+ * < 0.  Every argument check runs before the first HIP call and a refused call writes nothing. */
+typedef struct rvo3d_building_motion {
+  const double *ends;    /* [E][nb_max][2][2]: endpoint 0 and 1, x then y */
+  const double *speed;   /* [E][nb_max], metres per unit of dt            */
+  uint8_t *leg;          /* [E][nb_max] state: the endpoint being approached */
+} rvo3d_building_motion;
+int rvo3d_move_env_buildings(rvo3d_env *h, const rvo3d_building_motion *m, double dt, const uint8_t *env_mask,
+                             double *buildings_out, void *stream);
+
 /* Per-env drone counts: fleets of different sizes in one handle.  HOST counts [E], each 1..num_drones; NULL detaches
  * (every env has num_drones again).  Env e has the live drones 0 .. counts[e]-1; the rows d >= counts[e] are ghosts.  All
  * layouts stay [E][num_drones].  Env e behaves bit for bit as the env of a handle created with num_drones = counts[e] and

@@ -1,7 +1,8 @@
 """Secondary measurement: kernel time (HIP events on the launch stream) of the entry points next to
 the fused step at the benchmark shape - observe, plain step, step_policy (trainer glue fused in),
 reset + observe, des_vel, the classical RVO velocity selection.
-usage: python tools/bench_aux.py [--envs 4096 --drones 64]"""
+Last: moving buildings (move_buildings(): the launch, the host path for the same job, the env step of that world).
+usage: python tools/bench_aux.py [--envs 4096 --drones 64] [--only move_buildings]"""
 import argparse, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,13 +13,43 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--drones", type=int, default=64)
 ap.add_argument("--reps", type=int, default=100)
+ap.add_argument("--only", default=None, help="move_buildings: that entry alone")
 args = ap.parse_args()
 E, N = args.envs, args.drones
-env = BatchedDroneEnv(synthetic_world(E, N, (50.0, 50.0, 10.0)), neighbors_num=10, action_decimals=2)
-acts = [torch.from_numpy(synthetic_actions(E, N, t).astype(np.float32)).cuda() for t in range(16)]
-env.observe()
-for t in range(600):
-    env.step(acts[t % 16], autoreset=True)
+
+
+def move_buildings():
+    """Moving buildings (rvo3d_move_env_buildings) with 50 buildings per env on a 100 x 100 map: the launch, next to the
+    only thing the host path offers for the same job - one set_env_buildings call with the same sets (host staging,
+    hipMalloc, copies, a synchronisation: wall time) - and next to the env step of that configuration."""
+    import time
+    from rvo3d_amd import synthetic_patrols
+    world = synthetic_world(E, N, (100.0, 100.0, 10.0), nb=50, per_env_buildings=True)
+    env = BatchedDroneEnv(world, neighbors_num=10, action_decimals=2)
+    acts = [torch.from_numpy(synthetic_actions(E, N, t).astype(np.float32)).cuda() for t in range(16)]
+    env.observe()
+    for t in range(200):
+        env.step(acts[t % 16], autoreset=True)
+    step = timed("move_buildings: env step, static buildings", lambda i: env.step(acts[i % 16], autoreset=True))
+    motion = synthetic_patrols(world, seed=1, speed=(0.3, 1.5), span=6.0)
+    env.attach_building_motion(motion)
+    move = timed("move_buildings: the launch (50 per env)", lambda i: motion.advance(), per_drone=False)
+    both = timed("move_buildings: launch + env step", lambda i: env.step(acts[i % 16], autoreset=True))
+    env.attach_building_motion(None)
+    b, c = world.buildings, world.building_counts
+    env.set_env_buildings(b, c)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(10):
+        t0 = time.perf_counter()
+        env.set_env_buildings(b, c)
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    host = float(np.median(ts)) * 1e6
+    print("%-44s %8.1f us  (wall time, median of 10)" % ("move_buildings: one set_env_buildings call", host), flush=True)
+    print("move_buildings summary: launch %.1f us, host path %.1f us (%.0fx), env step %.1f us, launch + step %.1f us" % (
+        move, host, host / move, step, both), flush=True)
+    env.close()
 
 
 def timed(name, fn, bytes_per_drone=None, per_drone=True):
@@ -36,6 +67,16 @@ def timed(name, fn, bytes_per_drone=None, per_drone=True):
     print("%-44s %8.1f us%s" % (name, us, rate), flush=True)
     return us
 
+
+if args.only == "move_buildings":
+    move_buildings()
+    sys.exit(0)
+
+env = BatchedDroneEnv(synthetic_world(E, N, (50.0, 50.0, 10.0)), neighbors_num=10, action_decimals=2)
+acts = [torch.from_numpy(synthetic_actions(E, N, t).astype(np.float32)).cuda() for t in range(16)]
+env.observe()
+for t in range(600):
+    env.step(acts[t % 16], autoreset=True)
 
 W = env.W
 timed("step + auto-reset (fused, f32 actions)", lambda i: env.step(acts[i % 16], autoreset=True), 719)
@@ -87,3 +128,6 @@ for T in (16, 128):
         print("    %-40s %8.1f GB/s of its %d algorithmic bytes; transient memory %.1f MB" % (
             "", nbytes / us / 1e3, nbytes, (torch.cuda.max_memory_allocated() - base) / 1e6), flush=True)
     del rew, val, cut, cut3
+
+env.close()
+move_buildings()
