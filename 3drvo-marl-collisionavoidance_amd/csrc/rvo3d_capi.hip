@@ -1440,6 +1440,31 @@ int rvo3d_building_rows(rvo3d_env* h, const rvo3d_building_rows_args* a, void* s
   RVO3D_API_END
 }
 
+int rvo3d_building_rows_moving(rvo3d_env* h, const rvo3d_building_rows_args* a, const rvo3d_building_motion* m, double dt,
+                               void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  const char* why = "";
+  if (int rc = rvo3d::building_rows_moving_check(a, h->P.W, (int64_t)h->P.E * h->P.N, h->env_bld != nullptr, m, dt, &why))
+    return fail(rc, why);
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const int N = h->P.N, T = rvo3d::safety_threads(N);
+  const size_t epb = (size_t)(T / rvo3d::safety_lanes_per_env(N));
+  const rvo3d::BuildingRowsArgs A{a->k, a->reach, a->below, a->rows, a->row_ld, a->col0, a->b_count, a->obs};
+  const rvo3d::BuildingVelArgs V{m ? m->ends : nullptr, m ? m->speed : nullptr, m ? m->leg : nullptr, dt};
+  hipLaunchKernelGGL(h->counted ? rvo3d::building_rows_moving_counted_kernel : rvo3d::building_rows_moving_kernel,
+                     dim3((unsigned)(((size_t)h->P.E + epb - 1) / epb)), dim3((unsigned)T),
+                     rvo3d::building_lds_bytes(N, a->k, rvo3d::kBldRowFloatsMoving), static_cast<hipStream_t>(stream), h->P, A,
+                     V);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
 int rvo3d_set_reward_f64(rvo3d_env* h, double* reward64) {
   RVO3D_API_BEGIN
   if (!h) return fail(RVO3D_ERR_INVALID, "null handle");

@@ -43,6 +43,25 @@ __host__ __device__ inline MotionStep motion_move(double x, double y, uint8_t le
   }
   return m;
 }
+// The velocity the record's next motion_move will have shown, where the record stands now (include/rvo3d.h:
+// rvo3d_building_rows_moving, rule 2): the same step, d and branch; on arrival the move lands on T exactly, so the
+// velocity is the rest of the way over dt.  A static building: (0, 0), ends is not read.
+struct MotionVel { double x, y; };
+__host__ __device__ inline MotionVel motion_velocity(double x, double y, uint8_t leg, const double* ends, double speed,
+                                                     double dt) {
+  MotionVel v{0.0, 0.0};
+  const double step = speed * dt;
+  if (!(step > 0.0)) return v;
+  const int k = leg & 1;
+  const double dx = ends[2 * k] - x, dy = ends[2 * k + 1] - y;
+  const double d = __builtin_sqrt(dx * dx + dy * dy);
+  if (d <= step) {
+    v.x = dx / dt; v.y = dy / dt;
+  } else {
+    v.x = (dx / d) * speed; v.y = (dy / d) * speed;
+  }
+  return v;
+}
 
 // ---- the cell rule: what build_building_grid computes for one cell, u16 for u16 ----
 // a building's reach in the lists: min(largest drone radius + r_b, the 5 m gate) + 1e-3 (never NaN)

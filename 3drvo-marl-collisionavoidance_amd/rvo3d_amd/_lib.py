@@ -113,13 +113,13 @@ class EvalSafetyBufs(C.Structure):
 
 
 class BuildingRowsArgs(C.Structure):
-    """rvo3d_building_rows_args (rvo3d_building_rows)."""
+    """rvo3d_building_rows_args (rvo3d_building_rows, rvo3d_building_rows_moving)."""
     _fields_ = [("k", C.c_int32), ("reach", C.c_double), ("below", C.c_double), ("rows", C.c_void_p),
                 ("row_ld", C.c_int64), ("col0", C.c_int32), ("b_count", C.c_void_p), ("obs", C.c_void_p)]
 
 
 class BuildingMotionArgs(C.Structure):
-    """rvo3d_building_motion (rvo3d_move_env_buildings)."""
+    """rvo3d_building_motion (rvo3d_move_env_buildings, rvo3d_building_rows_moving)."""
     _fields_ = [("ends", C.c_void_p), ("speed", C.c_void_p), ("leg", C.c_void_p)]
 
 
@@ -142,6 +142,7 @@ SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_b
            "rvo3d_policy_rnn_tiles", "rvo3d_policy_rnn_tiles_x3_blob_bytes", "rvo3d_policy_rnn_tiles_x3_pack",
            "rvo3d_policy_rnn_tiles_x3", "rvo3d_reader_first_step", "rvo3d_rollout_account", "rvo3d_rollout_set_step_counter", "rvo3d_gae",
            "rvo3d_eval_action", "rvo3d_eval_account", "rvo3d_safety_scan", "rvo3d_eval_account_safety", "rvo3d_building_rows",
+           "rvo3d_building_rows_moving",
            "rvo3d_observe_envs", "rvo3d_set_reward_f64",
            "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
@@ -217,6 +218,7 @@ def lib():
     L.rvo3d_eval_account_safety.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_int64, C.POINTER(EvalBufs), C.c_double,
                                             C.POINTER(EvalSafetyBufs), vp]
     L.rvo3d_building_rows.argtypes = [vp, C.POINTER(BuildingRowsArgs), vp]
+    L.rvo3d_building_rows_moving.argtypes = [vp, C.POINTER(BuildingRowsArgs), C.POINTER(BuildingMotionArgs), C.c_double, vp]
     L.rvo3d_observe_envs.argtypes = [vp] * 7
     L.rvo3d_des_vel.argtypes = [vp, vp, vp]
     L.rvo3d_rvo_vel.argtypes = [vp, C.POINTER(C.c_double), C.c_double, vp, vp]

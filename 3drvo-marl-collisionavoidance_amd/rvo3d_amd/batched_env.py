@@ -418,22 +418,36 @@ class BatchedDroneEnv:
                                                 self._stream()), "rvo3d_safety_scan")
         return s
 
-    def building_rows(self, k: int = 4, reach: float = 5.0, below: float = 2.0):
+    def _motion_args(self):
+        """(rvo3d_building_motion or None, dt) of the motion attached now: what rvo3d_building_rows_moving takes."""
+        if self._motion is None:
+            return None, 0.0
+        return C.byref(self._motion._args), self._motion.dt
+
+    def building_rows(self, k: int = 4, reach: float = 5.0, below: float = 2.0, velocity: bool = False):
         """The k nearest buildings of every drone in the current state (rvo3d_building_rows; the rules are in
         include/rvo3d.h): (rows [E, N, k, 6] float32, b_count [E, N] int32).  A building counts when it passes the
         reference's gate (rvo_inter.preprocess: roof above p_z - below, centre within reach); a row is
         [dx, dy, dh, r_b, gap, urg], rounded to two decimals like the observation, rows by ascending gap, zeros from
-        b_count on and in ghost rows.  The env's persistent tensors (one pair per k), overwritten by the next call; one
-        launch, no synchronisation."""
-        k = int(k)
+        b_count on and in ghost rows.  velocity=True (rvo3d_building_rows_moving): rows [E, N, k, 8],
+        [dx, dy, dh, r_b, gap, urg_rel, vb_x, vb_y] - the urgency at the velocity relative to the building's and the
+        velocity the attached motion (attach_building_motion) gives the building on its next move, zeros without one.
+        The env's persistent tensors (one pair per k and width), overwritten by the next call; one launch, no
+        synchronisation."""
+        k, rf = int(k), 8 if velocity else 6
         cache = self.__dict__.setdefault("_bld_rows", {})
-        if k not in cache and 1 <= k <= 8:
-            cache[k] = (torch.zeros((self.E, self.N, k, 6), dtype=torch.float32, device=self.device),
-                        torch.zeros((self.E, self.N), dtype=torch.int32, device=self.device))
-        rows, cnt = cache.get(k, (None, None))
-        a = _lib.BuildingRowsArgs(k, float(reach), float(below), None if rows is None else rows.data_ptr(), 6 * k, 0,
+        if (k, rf) not in cache and 1 <= k <= 8:
+            cache[k, rf] = (torch.zeros((self.E, self.N, k, rf), dtype=torch.float32, device=self.device),
+                            torch.zeros((self.E, self.N), dtype=torch.int32, device=self.device))
+        rows, cnt = cache.get((k, rf), (None, None))
+        a = _lib.BuildingRowsArgs(k, float(reach), float(below), None if rows is None else rows.data_ptr(), rf * k, 0,
                                   None if cnt is None else cnt.data_ptr(), None)
-        _lib.check(_lib.lib().rvo3d_building_rows(self._h, C.byref(a), self._stream()), "rvo3d_building_rows")
+        if velocity:
+            m, dt = self._motion_args()
+            _lib.check(_lib.lib().rvo3d_building_rows_moving(self._h, C.byref(a), m, dt, self._stream()),
+                       "rvo3d_building_rows_moving")
+        else:
+            _lib.check(_lib.lib().rvo3d_building_rows(self._h, C.byref(a), self._stream()), "rvo3d_building_rows")
         return rows, cnt
 
     def des_vel(self):
@@ -567,9 +581,15 @@ class BuildingObsEnv(BatchedDroneEnv):
     pair the env owns (which keeps the plain env's zero-store reuse), then ONE widen launch into `obs` or the caller's
     obs_out [E, N, W]; reward, done, info, finish and vo_count are the plain env's.  Nothing is allocated after the first
     call and nothing synchronises.  Behind an auto-resetting step a reset drone's building rows are those of its reset
-    state (velocity 0: urg 0), like its re-observed row."""
+    state (velocity 0: urg 0), like its re-observed row.
 
-    def __init__(self, world, *args, building_rows: int = 4, reach: float = 5.0, below: float = 2.0, **kwargs):
+    building_velocity=True: rows of eight floats, [dx, dy, dh, r_b, gap, urg_rel, vb_x, vb_y] (rvo3d_building_rows_moving) -
+    W = 12 + 8k + 9 * nm, state_dim = 12 + 8k.  Every widen launch takes the building motion attached at that moment
+    (attach_building_motion), or none: attach, detach and set_env_buildings need no new env; without a motion the two
+    velocity floats are zeros and urg_rel is urg."""
+
+    def __init__(self, world, *args, building_rows: int = 4, reach: float = 5.0, below: float = 2.0,
+                 building_velocity: bool = False, **kwargs):
         k = int(building_rows)
         if not 1 <= k <= 8:
             raise ValueError("building_rows must be 1..8")
@@ -578,8 +598,10 @@ class BuildingObsEnv(BatchedDroneEnv):
         super().__init__(world, *args, **kwargs)
         self.building_k, self.reach, self.below = k, float(reach), float(below)
         self.W_dense = self.W
-        self.state_dim = 12 + 6 * k
-        self.W = self.W_dense + 6 * k
+        self.building_velocity = bool(building_velocity)
+        self.building_row_floats = 8 if self.building_velocity else 6
+        self.state_dim = 12 + self.building_row_floats * k
+        self.W = self.W_dense + self.building_row_floats * k
         self._dense = self.obs  # [E, N, W_dense]: what the step and the observation write; with vo_count the reuse pair
         self.obs = torch.zeros((self.E, self.N, self.W), dtype=torch.float32, device=self.device)
         self._dense_scratch = None
@@ -594,9 +616,15 @@ class BuildingObsEnv(BatchedDroneEnv):
         return po and pc, po or pc
 
     def _widen(self, out):
-        """dense + the building rows of the current state -> out [E, N, W] (rvo3d_building_rows, widen mode)."""
+        """dense + the building rows of the current state -> out [E, N, W] (rvo3d_building_rows or, with
+        building_velocity, rvo3d_building_rows_moving and the motion attached now; widen mode)."""
         self._wargs.rows = out.data_ptr()
-        _lib.check(_lib.lib().rvo3d_building_rows(self._h, C.byref(self._wargs), self._stream()), "rvo3d_building_rows")
+        if self.building_velocity:
+            m, dt = self._motion_args()
+            _lib.check(_lib.lib().rvo3d_building_rows_moving(self._h, C.byref(self._wargs), m, dt, self._stream()),
+                       "rvo3d_building_rows_moving")
+        else:
+            _lib.check(_lib.lib().rvo3d_building_rows(self._h, C.byref(self._wargs), self._stream()), "rvo3d_building_rows")
         return out
 
     def step(self, actions, autoreset: bool = False):

@@ -37,8 +37,9 @@ def _p(t):
 
 def check_state_dim(ac, env):
     """An rnn_ac reads the first state_dim floats of a row as the state and the rest as rows of 9; the env says how many
-    state floats its rows hold (BuildingObsEnv.state_dim = 12 + 6k; 12 without the attribute).  A reader made for another
-    number would take building floats for velocity obstacles - silently, where the difference is a multiple of 9."""
+    state floats its rows hold (BuildingObsEnv.state_dim = 12 + 6k, 12 + 8k with building_velocity; 12 without the
+    attribute).  A reader made for another number would take building floats for velocity obstacles - silently, where the
+    difference is a multiple of 9."""
     reader = getattr(getattr(ac, "pi", None), "rnn_reader", None)
     have, want = getattr(reader, "state_dim", None), int(getattr(env, "state_dim", 12))
     if have is not None and int(have) != want:

@@ -707,6 +707,42 @@ typedef struct rvo3d_building_rows_args {
 } rvo3d_building_rows_args;
 int rvo3d_building_rows(rvo3d_env *h, const rvo3d_building_rows_args *args, void *stream);
 
+/* rvo3d_building_rows for buildings that move (rvo3d_move_env_buildings): rows of EIGHT floats,
+ *   [ dx, dy, dh, r_b, gap, urg_rel, vb_x, vb_y ],
+ * the urgency taken at the drone's velocity relative to the building's - cal_exp_tim_with_building takes a relative
+ * velocity (rvo_inter.py:248-275) - and the building's velocity behind it.  args as for rvo3d_building_rows with 8k in
+ * place of 6k throughout: stand-alone mode writes the columns col0 .. col0 + 8k - 1 and needs row_ld >= col0 + 8k; widen
+ * mode writes [ 12 proprio | 8k building | 9 * nm VO ], needs col0 == 12 and row_ld >= W + 8k, leaves the columns behind
+ * W + 8k alone, and obs must not overlap the W + 8k floats of any row.  motion: HOST struct of the DEVICE pointers handed
+ * to rvo3d_move_env_buildings (nb_max that of the attached sets), all three read-only here, or NULL: every building stands.
+ * dt: that call's.
+ * The result is defined by these rules, to the last bit; every value is a float64, every operation rounded on its own (no
+ * FMA), a square is x * x, sqrt and / are correctly rounded, r2(v) = rint(v * 100.0) / 100.0 + 0.0.
+ *   1. Gate, gap, selection (the k smallest (gap, index)), b_count, the ordering, zero rows from b_count on and ghost
+ *      rows are rule for rule those of rvo3d_building_rows: for any motion the same buildings are kept in the same
+ *      slots, and columns 0..4 of every row of eight are bit for bit columns 0..4 of the row of six.
+ *   2. The velocity vb of the record b = (x, y, h, r) of env e where it stands now, as its next move will be, with
+ *      s = speed[e][b], T = ends[e][b][leg[e][b] & 1], step = s * dt:
+ *        motion == NULL, or !(step > 0) - speed 0, a NaN speed, dt 0: vb = (0, 0); ends is not read.
+ *        Else dx = T_x - x, dy = T_y - y, d = sqrt(dx*dx + dy*dy).  d <= step: vb = (dx / dt, dy / dt) - the next move
+ *        lands on T exactly.  Else vb = ((dx / d) * s, (dy / d) * s).
+ *      The same rule for every env (no env_mask is known here).  A filler (h == -inf) never passes the gate: nothing of
+ *      its motion is read.
+ *   3. urg_rel = 1.0 / (t + 0.2), t by rule 3 of rvo3d_building_rows at the velocity (v_x - vb_x, v_y - vb_y) in place of
+ *      (v_x, v_y); ex, ey and R as there.
+ *   4. Row, each as float32 of r2(.): the five columns of rule 1, r2(urg_rel), r2(vb_x), r2(vb_y).  No output is -0.0.
+ *   5. motion == NULL: columns 0..5 are rvo3d_building_rows' six floats bit for bit, columns 6 and 7 are +0.0.
+ * The launch is rvo3d_building_rows' (geometry, tiles, slots; the stage holds 8k + 1 dwords per lane); only the row
+ * writer differs: for each of its at most k kept records it also reads speed, leg and one endpoint.  One launch: no
+ * allocation, no synchronisation, no atomics.  The motion's buffers are the ones rvo3d_move_env_buildings writes: call
+ * both on the same stream, this one behind the step.  Graph capture with a motion stays the caller's to refuse.
+ * Every argument check runs before the first HIP call and a refused call writes nothing: what rvo3d_building_rows refuses
+ * (with 8k); RVO3D_ERR_STATE for a motion without attached per-env sets; RVO3D_ERR_INVALID for a null pointer inside
+ * motion and for dt not finite or < 0 (checked with and without a motion).  motion == NULL is allowed on any loaded
+ * handle, the shared list included. */
+int rvo3d_building_rows_moving(rvo3d_env *h, const rvo3d_building_rows_args *args,
+                               const rvo3d_building_motion *motion, double dt, void *stream);
+
 /* rvo3d_observe for the envs whose mask byte is non-zero (env_mask [E], required): their rows of obs / vo_count receive
  * bit for bit what rvo3d_observe writes, the other envs' rows are not written at all - an env in mid-episode keeps the
  * observation of its step (ir_gym.observation_reward, with the action), as in the reference, which observes with
