@@ -1508,6 +1508,33 @@ int rvo3d_rvo_vel(rvo3d_env* h, const double* vmax, double acceler, double* out_
   RVO3D_API_END
 }
 
+int rvo3d_rvo_vel_city(rvo3d_env* h, const rvo3d_rvo_city_args* a, const rvo3d_building_motion* m, double dt,
+                       void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  const char* why = "";
+  if (int rc = rvo3d::rvo_city_check(a, h->env_bld != nullptr, m, dt, &why)) return fail(rc, why);
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  rvo3d::RvoVelArgs A;
+  for (int k = 0; k < 3; ++k) A.vmax[k] = a->vmax[k];
+  A.acceler = a->acceler;
+  const rvo3d::RvoCityArgs Y{a->reach, a->below, a->horizon, a->clear_xy, a->clear_z, a->out_vel,
+                             reinterpret_cast<unsigned long long*>(a->live_mask),
+                             reinterpret_cast<unsigned long long*>(a->cone_mask),
+                             reinterpret_cast<unsigned long long*>(a->blocked_mask), a->tc_min, a->n_gated, a->tier};
+  const rvo3d::BuildingVelArgs V{m ? m->ends : nullptr, m ? m->speed : nullptr, m ? m->leg : nullptr, dt};
+  const int T = (int)align_up((size_t)h->P.N, 64);
+  hipLaunchKernelGGL(h->counted ? rvo3d::rvo_city_counted_kernel : rvo3d::rvo_city_kernel, dim3((unsigned)h->P.E),
+                     dim3((unsigned)T), (size_t)T * 8 * sizeof(double), static_cast<hipStream_t>(stream), h->P, A, Y, V);
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
 int rvo3d_state_ptrs(rvo3d_env* h, rvo3d_state_view* out) {
   RVO3D_API_BEGIN
   if (!h || !out) return fail(RVO3D_ERR_INVALID, "null argument");

@@ -123,6 +123,13 @@ class BuildingMotionArgs(C.Structure):
     _fields_ = [("ends", C.c_void_p), ("speed", C.c_void_p), ("leg", C.c_void_p)]
 
 
+class RvoCityArgs(C.Structure):
+    """rvo3d_rvo_city_args (rvo3d_rvo_vel_city)."""
+    _fields_ = [("vmax", C.c_double * 3), ("acceler", C.c_double), ("reach", C.c_double), ("below", C.c_double),
+                ("horizon", C.c_double), ("clear_xy", C.c_double), ("clear_z", C.c_double), ("out_vel", C.c_void_p)] + \
+               [(n, C.c_void_p) for n in ("live_mask", "cone_mask", "blocked_mask", "tc_min", "n_gated", "tier")]
+
+
 class StateView(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("px", "py", "pz", "vx", "vy", "vz", "yaw", "pitch", "real_len", "max_dev",
@@ -144,7 +151,7 @@ SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_b
            "rvo3d_eval_action", "rvo3d_eval_account", "rvo3d_safety_scan", "rvo3d_eval_account_safety", "rvo3d_building_rows",
            "rvo3d_building_rows_moving",
            "rvo3d_observe_envs", "rvo3d_set_reward_f64",
-           "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
+           "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_rvo_vel_city", "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
 
 # the symbols that return a byte count (int64, negative: shape not supported); every other one but
@@ -222,6 +229,7 @@ def lib():
     L.rvo3d_observe_envs.argtypes = [vp] * 7
     L.rvo3d_des_vel.argtypes = [vp, vp, vp]
     L.rvo3d_rvo_vel.argtypes = [vp, C.POINTER(C.c_double), C.c_double, vp, vp]
+    L.rvo3d_rvo_vel_city.argtypes = [vp, C.POINTER(RvoCityArgs), C.POINTER(BuildingMotionArgs), C.c_double, vp]
     L.rvo3d_state_ptrs.argtypes = [vp, C.POINTER(StateView)]
     L.rvo3d_get_state.argtypes = [vp] * 12
     L.rvo3d_set_state.argtypes = [vp] * 12

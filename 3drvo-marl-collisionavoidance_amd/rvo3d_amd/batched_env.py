@@ -464,6 +464,32 @@ class BatchedDroneEnv:
                    "rvo3d_rvo_vel")
         return out
 
+    def rvo_vel_city(self, vmax=(2.0, 2.0, 2.0), acceler: float = 0.5, horizon: float = 5.0, reach: float = 10.0,
+                     below: float = 1.0, clear_xy: float = 0.0, clear_z: float = 0.0, diagnostics: bool = False):
+        """rvo_vel that also keeps clear of the buildings (rvo3d_rvo_vel_city; the rules are in include/rvo3d.h): every
+        candidate velocity is swept against the cylinder of every building that passes the reference's gate
+        (reciprocal_vel_obs.preprocess: centre within `reach`, roof above p_z - `below`) over `horizon`, with `clear_xy` /
+        `clear_z` of extra clearance round the cylinder and over the roof; the choice is rvo_vel's among the candidates no
+        building blocks, and the one that hits last when all are blocked.  horizon=5.0 is the reference's 10 m gate over
+        its 2 m/s speed cap.  The buildings are the per-env sets while sets are attached, else the world's shared list;
+        the motion attached now (attach_building_motion) is picked up at every call: each candidate is then taken relative
+        to the velocity the building's next move will have.  Returns [E, N, 3] float64; with diagnostics=True also a dict
+        of what the selection was made from: live_mask, cone_mask, blocked_mask (int64, bit c = candidate c), tc_min
+        (float64), n_gated, tier (int32), [E, N] each.  One launch, no synchronisation."""
+        out = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
+        diag = {}
+        if diagnostics:
+            for name, dt_ in (("live_mask", torch.int64), ("cone_mask", torch.int64), ("blocked_mask", torch.int64),
+                              ("tc_min", torch.float64), ("n_gated", torch.int32), ("tier", torch.int32)):
+                diag[name] = torch.empty((self.E, self.N), dtype=dt_, device=self.device)
+        a = _lib.RvoCityArgs((C.c_double * 3)(*[float(x) for x in vmax]), float(acceler), float(reach), float(below),
+                             float(horizon), float(clear_xy), float(clear_z), out.data_ptr(),
+                             *[diag[n].data_ptr() if diagnostics else None
+                               for n in ("live_mask", "cone_mask", "blocked_mask", "tc_min", "n_gated", "tier")])
+        m, dt = self._motion_args()
+        _lib.check(_lib.lib().rvo3d_rvo_vel_city(self._h, C.byref(a), m, dt, self._stream()), "rvo3d_rvo_vel_city")
+        return (out, diag) if diagnostics else out
+
     # -- state ------------------------------------------------------------------------
     def get_state(self):
         E, N, dev = self.E, self.N, self.device

@@ -772,6 +772,70 @@ int rvo3d_des_vel(rvo3d_env *h, double *des_vel, void *stream);
 int rvo3d_rvo_vel(rvo3d_env *h, const double *vmax, double acceler, double *out_vel,
                   void *stream);
 
+/* rvo3d_rvo_vel that also keeps clear of the buildings, standing or moving (rvo3d_move_env_buildings): what
+ * reciprocal_vel_obs.preprocess collects as obs_list ("to be filled", reciprocal_vel_obs.py:46-52) and then drops.  Every
+ * candidate velocity is swept against the cylinder of every building near the drone over a look-ahead horizon, and the
+ * selection is made in four tiers.  motion, dt: as for rvo3d_building_rows_moving - motion is a HOST struct of the DEVICE
+ * pointers handed to rvo3d_move_env_buildings, read-only here, or NULL: every building stands (allowed on any loaded
+ * handle, the shared list included).
+ * The result is defined by these rules, to the last bit; every value is a float64, every operation rounded on its own (no
+ * FMA), a square is x * x, sqrt and / are correctly rounded, a minimum starts from +inf and takes x < m ? x : m.
+ *   0. Candidates.  The candidates, their numbering c = (ix * cnt_y + iy) * cnt_z + iz, their values, the live set
+ *      (|c| >= 0.3), the cone set (inside some neighbour's reciprocal cone) and tc_min (the least cal_exp_tim over the
+ *      neighbours within 10 m at the current velocity) are exactly rvo3d_rvo_vel's; live_mask, cone_mask and tc_min
+ *      report them.  des is the des_vel rvo3d_rvo_vel uses.
+ *   1. Buildings.  Env e's buildings are its per-env set while sets are attached, else the shared list, in index order.
+ *      The velocity vb of a record is rule 2 of rvo3d_building_rows_moving (the velocity its next move will have), (0, 0)
+ *      without a motion.  Gate (reciprocal_vel_obs.preprocess): ex = p_x - x_b, ey = p_y - y_b,
+ *      d = sqrt(ex*ex + ey*ey); b passes iff h_b > p_z - below and d <= reach.  A filler (h = -inf) fails, and nothing of
+ *      its motion is read.  n_gated is the number that pass.
+ *   2. Swept test, for a passing b and a live candidate (cx, cy, cz): R = (r + r_b) + clear_xy, H = h_b + clear_z,
+ *      wx = cx - vb_x, wy = cy - vb_y, a = wx*wx + wy*wy, bq = (2.0*ex)*wx + (2.0*ey)*wy, cq = (ex*ex + ey*ey) - R*R.
+ *        cq <= 0 (inside the clearance disk now): t_in = 0; t_out = +inf if a == 0, else
+ *          (-bq + sqrt(bq*bq - (4.0*a)*cq)) / (2.0*a).
+ *        Else disc = bq*bq - (4.0*a)*cq; disc <= 0: b does not block c.  s = sqrt(disc), t_in = (-bq - s) / (2.0*a),
+ *          t_out = (-bq + s) / (2.0*a); !(t_in >= 0): b does not block c (moving away).
+ *      b blocks c iff t_in <= horizon and zmin <= H, with te = t_out < horizon ? t_out : horizon, z_in = p_z + cz*t_in,
+ *      z_e = p_z + cz*te, zmin = z_e < z_in ? z_e : z_in: the exact sweep of the drone's centre against the cylinder over
+ *      the horizon.  A candidate that climbs over the roof before it arrives is free; one that sinks onto a roof it hovers
+ *      over is blocked.  Bit c of blocked_mask is the OR over the passing buildings; tb(c) is the minimum of t_in over the
+ *      buildings that block c.  For finite state whose squares do not overflow no NaN arises: inside the disk the root is
+ *      taken of a sum of two non-negative numbers, outside of disc > 0 only, a quotient 0/0 (a == 0 by underflow) fails
+ *      t_in >= 0, and a blocking t_in lies in [0, horizon].  OR and minimum do not depend on the order of the buildings,
+ *      so the tile order cannot show in the result.
+ *   3. Selection, dd(c) rvo3d_rvo_vel's distance to des, "first" the lowest c:
+ *        tier 1: live & ~cone & ~blocked not empty - the least dd, first among equals;
+ *        tier 2: else live & ~blocked not empty - the least 1 * tc_inv + dd (rvo3d_rvo_vel's inside rule), first among
+ *                equals: buildings do not give way, drones do;
+ *        tier 3: else live not empty - the largest tb(c), then the least dd, then the first: every candidate hits
+ *                something within the horizon, so take the one that hits last;
+ *        tier 4: else out_vel = 0.
+ *      A live row's tier is 1..4.
+ *   4. Ghost rows (counted handle, d >= counts[e]): out_vel 0 and every diagnostic 0 (tier 0); the ghost's state is not read.
+ *   5. When no building passes the gate for a drone, tiers 1 and 2 are rvo3d_rvo_vel's two cases and its out_vel row is
+ *      rvo3d_rvo_vel's, bit for bit.
+ * rvo3d_rvo_vel's geometry: one workgroup per env, one lane per drone; the building records go through LDS in tiles, the
+ * velocity of a record computed once by the lane that loads it; the planar roots are taken once per building and
+ * (ix, iy); tier 3 is a second trip over the tiles, entered only when some drone of the env needs it.  One launch: no
+ * allocation, no synchronisation, no atomics.  Call it on the stream of rvo3d_move_env_buildings.  Graph capture with a
+ * motion stays the caller's to refuse.
+ * Every argument check runs before the first HIP call and a refused call writes nothing: RVO3D_ERR_STATE without a loaded
+ * world, or for a motion without attached per-env sets; RVO3D_ERR_INVALID for a null args / out_vel / pointer inside
+ * motion, for acceler outside [0, 1], for each non-finite or out-of-range double, and for dt not finite or < 0 (checked
+ * with and without a motion). */
+typedef struct rvo3d_rvo_city_args {
+  double vmax[3]; double acceler;          /* as rvo3d_rvo_vel: 0 <= acceler <= 1                          */
+  double reach, below;                     /* building gate, finite > 0 / finite >= 0 (reference: 10, 1)   */
+  double horizon;                          /* finite > 0: look-ahead, in the time unit of the velocities   */
+  double clear_xy, clear_z;                /* finite >= 0: extra clearance round the cylinder / over the roof */
+  double *out_vel;                         /* DEVICE [E][N][3], required                                   */
+  /* DEVICE, each nullable: what the selection was made from (tests, diagnostics) */
+  uint64_t *live_mask, *cone_mask, *blocked_mask;   /* [E][N], bit c = candidate c  */
+  double *tc_min;  int32_t *n_gated, *tier;         /* [E][N]                        */
+} rvo3d_rvo_city_args;
+int rvo3d_rvo_vel_city(rvo3d_env *h, const rvo3d_rvo_city_args *args,
+                       const rvo3d_building_motion *motion, double dt, void *stream);
+
 /* Zero-copy views of the state arrays, READ-ONLY: the step keeps values derived from the
  * state on file between calls (des_vel, the in-range words of the pair gate, the current /
  * previous waypoint); state is changed through rvo3d_set_state / rvo3d_reset*, which bring
