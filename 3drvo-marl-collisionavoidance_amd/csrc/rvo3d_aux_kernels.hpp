@@ -4,6 +4,7 @@
 #pragma once
 
 #include "rvo3d_step.hpp"
+#include "rvo3d_rvo_rules.hpp"
 
 namespace rvo3d {
 
@@ -118,59 +119,47 @@ __device__ __forceinline__ double arange_at(double lo, int k) {  // numpy fills 
   return k == 0 ? lo : (k == 1 ? next : lo + k * (next - lo));
 }
 
-// CNT (rvo_vel_counted_kernel): the env's drones are the first live_drones(P, e) of its P.N rows; the ghosts are invisible
-// to them and their own rows are zero.
-template <bool CNT>
-__device__ __forceinline__ void rvo_vel_body(const Params P, const RvoVelArgs A, double* out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int d = threadIdx.x, e = blockIdx.x;
-  const int N = CNT ? live_drones(P, e) : P.N;  // the drones the env has
-  const int T = blockDim.x;
-  double* const lx = reinterpret_cast<double*>(smem);  // x y z vx vy vz r prio, [T] each
-  const bool active = d < N;
-  const int g = active ? e * P.N + d : e * P.N;
-  if (CNT && !active && d < P.N) {
-    double* o = out + 3 * ((size_t)e * P.N + d);
-    o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
-  }
-  Drone S;
-  S.x = P.px()[g]; S.y = P.py()[g]; S.z = P.pz()[g];
-  S.vx = P.vx()[g]; S.vy = P.vy()[g]; S.vz = P.vz()[g];
-  S.r = P.radius()[g]; S.prio = P.prio()[g];
-  lx[d] = S.x; lx[T + d] = S.y; lx[2 * T + d] = S.z;
-  lx[3 * T + d] = S.vx; lx[4 * T + d] = S.vy; lx[5 * T + d] = S.vz;
-  lx[6 * T + d] = S.r; lx[7 * T + d] = S.prio;
-  __syncthreads();
-  if (!active) return;
-  double cur[3], des[3];
-  load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
-  const double p[3] = {S.x, S.y, S.z}, v0[3] = {S.vx, S.vy, S.vz};
-  des_vel(P, p, cur, des);
-  double lo[3];
-  int cnt[3];
+// rvo_vel_body's drone side in three pieces: the candidate grid, the neighbour scan and the selection
+// (rvo3d_rvo_rules.hpp: rvo_select).  rvo_city_body (rvo3d_rvo_city_kernels.hpp) shares the selection and restates the
+// other two, for the speed of its kernel; its header comment has the figures.  A change here is a change there.
+
+// The candidates of a drone flying at v0: per axis np.arange(lo, hi, 0.5) over the clipped [v0 - acceler, v0 + acceler],
+// at most 4 values (the host checks acceler <= 1); candidate c = (ix * cnt1 + iy) * cnt2 + iz - nested loops, no
+// division by the runtime counts - is live unless slower than 0.3 m/s.  Fills lo[3] and cnt[3], returns the live mask.
+__device__ __forceinline__ unsigned long long rvo_grid(const RvoVelArgs& A, const double* v0, double* lo, int* cnt) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     lo[k] = clampd(v0[k] - A.acceler, -A.vmax[k], A.vmax[k]);  // np.clip
     const double hi = clampd(v0[k] + A.acceler, -A.vmax[k], A.vmax[k]);
     cnt[k] = arange_len(lo[k], hi);
-    if (cnt[k] > 4) cnt[k] = 4;  // host checks acceler <= 1
+    if (cnt[k] > 4) cnt[k] = 4;
   }
-  unsigned long long live = 0ull, inside = 0ull;
-  // candidate c = (ix * cnt1 + iy) * cnt2 + iz: nested loops, no division by the runtime counts
-  {
-    int c = 0;
-    for (int ix = 0; ix < cnt[0]; ++ix)
-      for (int iy = 0; iy < cnt[1]; ++iy)
-        for (int iz = 0; iz < cnt[2]; ++iz, ++c)
-          if (!(__builtin_sqrt(sq(arange_at(lo[0], ix)) + sq(arange_at(lo[1], iy)) + sq(arange_at(lo[2], iz))) < 0.3))
-            live |= 1ull << c;
-  }
+  unsigned long long live = 0ull;
+  int c = 0;
+  for (int ix = 0; ix < cnt[0]; ++ix)
+    for (int iy = 0; iy < cnt[1]; ++iy)
+      for (int iz = 0; iz < cnt[2]; ++iz, ++c)
+        if (!(__builtin_sqrt(sq(arange_at(lo[0], ix)) + sq(arange_at(lo[1], iy)) + sq(arange_at(lo[2], iz))) < 0.3))
+          live |= 1ull << c;
+  return live;
+}
+
+// Drone d (record S) against the N - 1 others of its env, their records in LDS (lx: x y z vx vy vz r prio, [T] each),
+// those within 10 m (T10: the squared gate): the least expected collision time and, one bit per live candidate, whether
+// it lies inside some neighbour's velocity obstacle.
+struct RvoCones {
+  double tc_min;
+  unsigned long long inside;
+};
+__device__ __forceinline__ RvoCones rvo_neighbours(const Drone S, const double* lx, int T, int N, int d, double T10,
+                                                   const double* lo, const int* cnt, unsigned long long live) {
   double tc_min = __builtin_inf();
+  unsigned long long inside = 0ull;
   for (int j = 0; j < N; ++j) {
     if (j == d) continue;
     const double bx = lx[j], by = lx[T + j], bz = lx[2 * T + j];
     const double fx = S.x - bx, fy = S.y - by, fz = S.z - bz;  // agent - drone (:40-43)
-    if (!(dot3b(fx, fy, fz, fx, fy, fz) <= P.T10)) continue;   // norm <= 10
+    if (!(dot3b(fx, fy, fz, fx, fy, fz) <= T10)) continue;     // norm <= 10
     const double bvx = lx[3 * T + j], bvy = lx[4 * T + j], bvz = lx[5 * T + j];
     const double br = lx[6 * T + j], bprio = lx[7 * T + j];
     // cal_exp_tim (vel_obs3D.py:104-143)
@@ -235,29 +224,45 @@ __device__ __forceinline__ void rvo_vel_body(const Params P, const RvoVelArgs A,
       }
     }
   }
-  const double tc_inv = (tc_min == 0) ? __builtin_inf() : 1.0 / tc_min;
-  bool have_out = false, have_in = false;
-  double best_out = 0, best_in = 0, so[3] = {0, 0, 0}, si[3] = {0, 0, 0};
-  {  // vel_select (:119-124): Python min keeps the first minimum
-    int c = 0;
-    for (int ix = 0; ix < cnt[0]; ++ix)
-      for (int iy = 0; iy < cnt[1]; ++iy)
-        for (int iz = 0; iz < cnt[2]; ++iz, ++c) {
-          if (!((live >> c) & 1ull)) continue;
-          const double vx = arange_at(lo[0], ix), vy = arange_at(lo[1], iy), vz = arange_at(lo[2], iz);
-          const double dd = __builtin_sqrt(sq(des[0] - vx) + sq(des[1] - vy) + sq(des[2] - vz));
-          if (!((inside >> c) & 1ull)) {
-            if (!have_out || dd < best_out) { best_out = dd; so[0] = vx; so[1] = vy; so[2] = vz; have_out = true; }
-          } else {
-            const double pen = 1 * tc_inv + dd;
-            if (!have_in || pen < best_in) { best_in = pen; si[0] = vx; si[1] = vy; si[2] = vz; have_in = true; }
-          }
-        }
+  return RvoCones{tc_min, inside};
+}
+
+// CNT (rvo_vel_counted_kernel): the env's drones are the first live_drones(P, e) of its P.N rows; the ghosts are invisible
+// to them and their own rows are zero.
+template <bool CNT>
+__device__ __forceinline__ void rvo_vel_body(const Params P, const RvoVelArgs A, double* out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int d = threadIdx.x, e = blockIdx.x;
+  const int N = CNT ? live_drones(P, e) : P.N;  // the drones the env has
+  const int T = blockDim.x;
+  double* const lx = reinterpret_cast<double*>(smem);  // x y z vx vy vz r prio, [T] each
+  const bool active = d < N;
+  const int g = active ? e * P.N + d : e * P.N;
+  if (CNT && !active && d < P.N) {
+    double* o = out + 3 * ((size_t)e * P.N + d);
+    o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
   }
+  Drone S;
+  S.x = P.px()[g]; S.y = P.py()[g]; S.z = P.pz()[g];
+  S.vx = P.vx()[g]; S.vy = P.vy()[g]; S.vz = P.vz()[g];
+  S.r = P.radius()[g]; S.prio = P.prio()[g];
+  lx[d] = S.x; lx[T + d] = S.y; lx[2 * T + d] = S.z;
+  lx[3 * T + d] = S.vx; lx[4 * T + d] = S.vy; lx[5 * T + d] = S.vz;
+  lx[6 * T + d] = S.r; lx[7 * T + d] = S.prio;
+  __syncthreads();
+  if (!active) return;
+  double cur[3], des[3];
+  load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
+  const double p[3] = {S.x, S.y, S.z}, v0[3] = {S.vx, S.vy, S.vz};
+  des_vel(P, p, cur, des);
+  double lo[3];
+  int cnt[3];
+  const unsigned long long live = rvo_grid(A, v0, lo, cnt);
+  const RvoCones nb = rvo_neighbours(S, lx, T, N, d, P.T10, lo, cnt, live);
   double* o = out + 3 * (size_t)g;
-  if (have_out) { o[0] = so[0]; o[1] = so[1]; o[2] = so[2]; }
-  else if (have_in) { o[0] = si[0]; o[1] = si[1]; o[2] = si[2]; }
-  else { o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; }
+  if (!rvo_select(cnt, [&](int k, int i) { return arange_at(lo[k], i); }, des, nb.tc_min, live, nb.inside, 0ull, o)) {
+    o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
+  }
 }
 __global__ void __launch_bounds__(512) rvo_vel_kernel(const Params P, const RvoVelArgs A, double* out) {
   rvo_vel_body<false>(P, A, out);

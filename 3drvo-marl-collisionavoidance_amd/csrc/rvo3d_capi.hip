@@ -1360,17 +1360,35 @@ int rvo3d_eval_account(rvo3d_env* h, const float* reward, const uint8_t* done, c
 }  // extern "C"
 
 namespace {
-// the scan's launch for both entry points below (arguments checked, device entered)
-int launch_safety_scan(rvo3d_env* h, const rvo3d::SafetyArgs& A, hipStream_t s) {
+// the launch geometry of the kernels with one lane per drone and whole envs per block (safety_scan_body's)
+struct EnvLanes {
+  dim3 grid, block;
+};
+EnvLanes env_lanes(const rvo3d_env* h) {
   const int N = h->P.N, T = rvo3d::safety_threads(N);
   const size_t epb = (size_t)(T / rvo3d::safety_lanes_per_env(N));
-  hipLaunchKernelGGL(h->counted ? rvo3d::safety_scan_counted_kernel : rvo3d::safety_scan_kernel,
-                     dim3((unsigned)(((size_t)h->P.E + epb - 1) / epb)), dim3((unsigned)T), rvo3d::safety_lds_bytes(N), s,
-                     h->P, A);
+  return EnvLanes{dim3((unsigned)(((size_t)h->P.E + epb - 1) / epb)), dim3((unsigned)T)};
+}
+// the scan's launch for both entry points below (arguments checked, device entered)
+int launch_safety_scan(rvo3d_env* h, const rvo3d::SafetyArgs& A, hipStream_t s) {
+  const EnvLanes g = env_lanes(h);
+  hipLaunchKernelGGL(h->counted ? rvo3d::safety_scan_counted_kernel : rvo3d::safety_scan_kernel, g.grid, g.block,
+                     rvo3d::safety_lds_bytes(h->P.N), s, h->P, A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
 }
 bool near_margin_ok(double m) { return std::isfinite(m) && m >= 0.0; }
+// the building velocities' arguments: no motion, no velocity
+rvo3d::BuildingVelArgs building_vel_args(const rvo3d_building_motion* m, double dt) {
+  return rvo3d::BuildingVelArgs{m ? m->ends : nullptr, m ? m->speed : nullptr, m ? m->leg : nullptr, dt};
+}
+// the classical RVO velocity's arguments; false: acceler is refused (rvo3d::kRvoAccelerWhy)
+bool rvo_vel_args(const double* vmax, double acceler, rvo3d::RvoVelArgs* A) {
+  if (!rvo3d::rvo_acceler_ok(acceler)) return false;
+  for (int k = 0; k < 3; ++k) A->vmax[k] = vmax[k];
+  A->acceler = acceler;
+  return true;
+}
 }  // namespace
 
 extern "C" {
@@ -1429,12 +1447,10 @@ int rvo3d_building_rows(rvo3d_env* h, const rvo3d_building_rows_args* a, void* s
   DeviceGuard dg;
   int rc = check(h, true, dg);
   if (rc) return rc;
-  const int N = h->P.N, T = rvo3d::safety_threads(N);
-  const size_t epb = (size_t)(T / rvo3d::safety_lanes_per_env(N));
+  const EnvLanes g = env_lanes(h);
   const rvo3d::BuildingRowsArgs A{a->k, a->reach, a->below, a->rows, a->row_ld, a->col0, a->b_count, a->obs};
-  hipLaunchKernelGGL(h->counted ? rvo3d::building_rows_counted_kernel : rvo3d::building_rows_kernel,
-                     dim3((unsigned)(((size_t)h->P.E + epb - 1) / epb)), dim3((unsigned)T),
-                     rvo3d::building_lds_bytes(N, a->k), static_cast<hipStream_t>(stream), h->P, A);
+  hipLaunchKernelGGL(h->counted ? rvo3d::building_rows_counted_kernel : rvo3d::building_rows_kernel, g.grid, g.block,
+                     rvo3d::building_lds_bytes(h->P.N, a->k), static_cast<hipStream_t>(stream), h->P, A);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END
@@ -1452,14 +1468,11 @@ int rvo3d_building_rows_moving(rvo3d_env* h, const rvo3d_building_rows_args* a, 
   DeviceGuard dg;
   int rc = check(h, true, dg);
   if (rc) return rc;
-  const int N = h->P.N, T = rvo3d::safety_threads(N);
-  const size_t epb = (size_t)(T / rvo3d::safety_lanes_per_env(N));
+  const EnvLanes g = env_lanes(h);
   const rvo3d::BuildingRowsArgs A{a->k, a->reach, a->below, a->rows, a->row_ld, a->col0, a->b_count, a->obs};
-  const rvo3d::BuildingVelArgs V{m ? m->ends : nullptr, m ? m->speed : nullptr, m ? m->leg : nullptr, dt};
-  hipLaunchKernelGGL(h->counted ? rvo3d::building_rows_moving_counted_kernel : rvo3d::building_rows_moving_kernel,
-                     dim3((unsigned)(((size_t)h->P.E + epb - 1) / epb)), dim3((unsigned)T),
-                     rvo3d::building_lds_bytes(N, a->k, rvo3d::kBldRowFloatsMoving), static_cast<hipStream_t>(stream), h->P, A,
-                     V);
+  hipLaunchKernelGGL(h->counted ? rvo3d::building_rows_moving_counted_kernel : rvo3d::building_rows_moving_kernel, g.grid,
+                     g.block, rvo3d::building_lds_bytes(h->P.N, a->k, rvo3d::kBldRowFloatsMoving),
+                     static_cast<hipStream_t>(stream), h->P, A, building_vel_args(m, dt));
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END
@@ -1494,11 +1507,8 @@ int rvo3d_rvo_vel(rvo3d_env* h, const double* vmax, double acceler, double* out_
   int rc = check(h, true, dg);
   if (rc) return rc;
   if (!vmax || !out_vel) return fail(RVO3D_ERR_INVALID, "vmax / out_vel are required");
-  if (!(acceler >= 0.0 && acceler <= 1.0))
-    return fail(RVO3D_ERR_INVALID, "acceler must be in [0, 1] (at most 4 candidates per axis)");
   rvo3d::RvoVelArgs A;
-  for (int k = 0; k < 3; ++k) A.vmax[k] = vmax[k];
-  A.acceler = acceler;
+  if (!rvo_vel_args(vmax, acceler, &A)) return fail(RVO3D_ERR_INVALID, rvo3d::kRvoAccelerWhy);
   const int T = (int)align_up((size_t)h->P.N, 64);
   hipLaunchKernelGGL(h->counted ? rvo3d::rvo_vel_counted_kernel : rvo3d::rvo_vel_kernel, dim3((unsigned)h->P.E),
                      dim3((unsigned)T),
@@ -1516,20 +1526,19 @@ int rvo3d_rvo_vel_city(rvo3d_env* h, const rvo3d_rvo_city_args* a, const rvo3d_b
   if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
   const char* why = "";
   if (int rc = rvo3d::rvo_city_check(a, h->env_bld != nullptr, m, dt, &why)) return fail(rc, why);
+  rvo3d::RvoVelArgs A;
+  if (!rvo_vel_args(a->vmax, a->acceler, &A)) return fail(RVO3D_ERR_INVALID, rvo3d::kRvoAccelerWhy);
   DeviceGuard dg;
   int rc = check(h, true, dg);
   if (rc) return rc;
-  rvo3d::RvoVelArgs A;
-  for (int k = 0; k < 3; ++k) A.vmax[k] = a->vmax[k];
-  A.acceler = a->acceler;
   const rvo3d::RvoCityArgs Y{a->reach, a->below, a->horizon, a->clear_xy, a->clear_z, a->out_vel,
                              reinterpret_cast<unsigned long long*>(a->live_mask),
                              reinterpret_cast<unsigned long long*>(a->cone_mask),
                              reinterpret_cast<unsigned long long*>(a->blocked_mask), a->tc_min, a->n_gated, a->tier};
-  const rvo3d::BuildingVelArgs V{m ? m->ends : nullptr, m ? m->speed : nullptr, m ? m->leg : nullptr, dt};
   const int T = (int)align_up((size_t)h->P.N, 64);
   hipLaunchKernelGGL(h->counted ? rvo3d::rvo_city_counted_kernel : rvo3d::rvo_city_kernel, dim3((unsigned)h->P.E),
-                     dim3((unsigned)T), (size_t)T * 8 * sizeof(double), static_cast<hipStream_t>(stream), h->P, A, Y, V);
+                     dim3((unsigned)T), (size_t)T * 8 * sizeof(double), static_cast<hipStream_t>(stream), h->P, A, Y,
+                     building_vel_args(m, dt));
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END

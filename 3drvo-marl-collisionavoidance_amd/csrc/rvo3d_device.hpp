@@ -28,7 +28,8 @@
 // Files: rvo3d_params.hpp (parameter blocks), rvo3d_host_setup.hpp (what the host derives for a handle: bands,
 // launch geometry, tables, the staged world; host only), rvo3d_math.hpp (arithmetic model, per-drone
 // pieces), rvo3d_lds.hpp (LDS views), rvo3d_pairs.hpp (pair pipeline), rvo3d_step.hpp (the step
-// kernel), rvo3d_aux_kernels.hpp (resets, tables, classical RVO selection), rvo3d_rollout_kernels.hpp (the
+// kernel), rvo3d_aux_kernels.hpp (resets, tables, classical RVO selection), rvo3d_rvo_rules.hpp (that selection's
+// plain-C++ part: the acceler check, the choice among the candidates), rvo3d_rollout_kernels.hpp (the
 // trainer's per-step glue: policy heads + sampling, episode bookkeeping), rvo3d_route_kernels.hpp (routes re-drawn on
 // the device: per-env replacement, the Philox start / goal sampler), rvo3d_eval_kernels.hpp (the evaluator's:
 // action glue, episode records, per-env re-observation), rvo3d_safety_kernels.hpp (safety metrics of the current state:

@@ -3,13 +3,15 @@
 // of the env's buildings - standing or moving (rvo3d_move_env_buildings) - over a look-ahead horizon, and a selection in
 // four tiers.  What reciprocal_vel_obs.preprocess collects as obs_list and then drops.
 // Part of the gfx950 device code (see rvo3d_device.hpp for the overview).
-// The building arithmetic (rules 1-3), the selection and the argument checks are plain C++ (__host__ __device__ / host):
+// The building arithmetic (rules 1-3), the selection (rvo3d_rvo_rules.hpp: rvo_select, shared with rvo_vel_body) and the
+// argument checks are plain C++ (__host__ __device__ / host):
 // tests/host/rvo_city_check.hip calls them on the CPU (it defines RVO3D_RVO_CITY_RULES_ONLY: the kernels below need the
 // whole device code in front of them).
 #pragma once
 
 #include "../../include/rvo3d.h"
 #include "rvo3d_building_kernels.hpp"
+#include "rvo3d_rvo_rules.hpp"
 
 namespace rvo3d {
 
@@ -57,35 +59,14 @@ __host__ __device__ inline bool city_blocks(const CityRoots& q, double pz, doubl
 }
 
 // ---- rule 3 ----
-// Tiers 1 and 2 over the candidates c = (ix * cnt[1] + iy) * cnt[2] + iz with the values val(axis, i): rvo_vel_body's
-// vel_select over live & ~blocked.  1: outside every cone, closest to des; 2: none such - the least 1 * tc_inv + dd;
-// 0: every live candidate is blocked (tier 3) or none is live (tier 4), o is not written.
+// Tiers 1 and 2 are rvo_vel_body's selection (rvo3d_rvo_rules.hpp: rvo_select) over live & ~blocked; its 0 is tier 3
+// (every live candidate is blocked) or tier 4 (none is live), o is not written.  The rule's name, as
+// tests/host/rvo_city_check.hip calls it:
 template <class Val>
 __host__ __device__ inline int city_select(const int* cnt, Val val, const double* des, double tc_min,
                                            unsigned long long live, unsigned long long cone, unsigned long long blocked,
                                            double* o) {
-  const unsigned long long free_ = live & ~blocked;
-  const double tc_inv = (tc_min == 0) ? safety_inf() : 1.0 / tc_min;
-  bool have_out = false, have_in = false;
-  double best_out = 0, best_in = 0, so[3] = {0, 0, 0}, si[3] = {0, 0, 0};
-  int c = 0;
-  for (int ix = 0; ix < cnt[0]; ++ix)
-    for (int iy = 0; iy < cnt[1]; ++iy)
-      for (int iz = 0; iz < cnt[2]; ++iz, ++c) {
-        if (!((free_ >> c) & 1ull)) continue;
-        const double vx = val(0, ix), vy = val(1, iy), vz = val(2, iz);
-        const double ax = des[0] - vx, ay = des[1] - vy, az = des[2] - vz;
-        const double dd = __builtin_sqrt(ax * ax + ay * ay + az * az);
-        if (!((cone >> c) & 1ull)) {
-          if (!have_out || dd < best_out) { best_out = dd; so[0] = vx; so[1] = vy; so[2] = vz; have_out = true; }
-        } else {
-          const double pen = 1 * tc_inv + dd;
-          if (!have_in || pen < best_in) { best_in = pen; si[0] = vx; si[1] = vy; si[2] = vz; have_in = true; }
-        }
-      }
-  if (have_out) { o[0] = so[0]; o[1] = so[1]; o[2] = so[2]; return 1; }
-  if (have_in) { o[0] = si[0]; o[1] = si[1]; o[2] = si[2]; return 2; }
-  return 0;
+  return rvo_select(cnt, val, des, tc_min, live, cone, blocked, o);
 }
 // Tier 3, candidates offered in ascending c: the largest tb, then the least dd, then the first
 struct CityLast {
@@ -107,7 +88,7 @@ inline int rvo_city_check(const rvo3d_rvo_city_args* a, bool sets_attached, cons
   *why = "";
   if (!a) { *why = "null rvo3d_rvo_city_args"; return RVO3D_ERR_INVALID; }
   if (!a->out_vel) { *why = "out_vel is required"; return RVO3D_ERR_INVALID; }
-  if (!(a->acceler >= 0.0 && a->acceler <= 1.0)) { *why = "acceler must be in [0, 1] (at most 4 candidates per axis)"; return RVO3D_ERR_INVALID; }
+  if (!rvo_acceler_ok(a->acceler)) { *why = kRvoAccelerWhy; return RVO3D_ERR_INVALID; }
   if (!building_finite(a->reach) || !(a->reach > 0.0)) { *why = "reach must be finite and > 0"; return RVO3D_ERR_INVALID; }
   if (!building_finite(a->below) || !(a->below >= 0.0)) { *why = "below must be finite and >= 0"; return RVO3D_ERR_INVALID; }
   if (!building_finite(a->horizon) || !(a->horizon > 0.0)) { *why = "horizon must be finite and > 0"; return RVO3D_ERR_INVALID; }
@@ -130,8 +111,13 @@ struct RvoCityArgs {
 };
 
 // rvo_vel_body's geometry: one workgroup per env, one lane per drone, T = align_up(N, 64) threads, the env's drone
-// records in LDS (8 T doubles).  The drone part below is rvo_vel_body's text, copied: shared through a function it cost
-// rvo_vel_kernel two VGPRs, and that kernel's machine code stays what it was.  Behind it the same LDS takes the building
+// records in LDS (8 T doubles).  The selection is shared with rvo_vel_body (rvo3d_rvo_rules.hpp: rvo_select).  The grid
+// and the neighbour scan below still restate rvo_grid and rvo_neighbours (rvo3d_aux_kernels.hpp), which rvo_vel_body
+// calls: called from here they kept 166 VGPRs, 3 waves, no scratch and a neighbour loop with the same instructions, but
+// other registers in it, and on the MI355X that kernel was 3 % (acceler 0.5) to 6 % (acceler 1) slower than this text
+// (profiles/rvo_side_shared/measurements.txt).  Rule 5 - nothing in reach: the row is rvo_vel's - needs the two to stay
+// the same arithmetic; tests/test_rvo_vel.py holds this kernel to rvo_vel's bits on the states the oracle pins.  Behind
+// the drone side the same LDS takes the building
 // records in tiles of T - x y h r and the velocity the loading lane computed, 6 T doubles - which every lane reads as a
 // broadcast.  The fast path keeps three 64-bit masks per lane.  Tier 3 needs tb(c) per candidate: a second trip over the
 // tiles per planar candidate (ix, iy) some lane of the workgroup needs (a workgroup-wide vote through LDS: the barriers
@@ -158,7 +144,7 @@ __device__ __forceinline__ void rvo_city_body(const Params& P, const RvoVelArgs&
   int cnt[3] = {0, 0, 0};
   unsigned long long live = 0ull, inside = 0ull;
   double tc_min = __builtin_inf();
-  if (active) {  // ---- the drone part: rvo_vel_body's ----
+  if (active) {  // ---- the drone side: rvo_grid and rvo_neighbours, restated (see above) ----
     double cur[3];
     load3(P.cur(0), P.cur(1), P.cur(2), g, cur);
     const double p[3] = {S.x, S.y, S.z}, v0[3] = {S.vx, S.vy, S.vz};
@@ -213,8 +199,8 @@ __device__ __forceinline__ void rvo_city_body(const Params& P, const RvoVelArgs&
       const double pr = S.prio / (S.prio + bprio);                            // get_PAA
       const double pax = pr * (2 * S.x + (S.vx + bvx) * 1), pay = pr * (2 * S.y + (S.vy + bvy) * 1),
                    paz = pr * (2 * S.z + (S.vz + bvz) * 1);
-      // the shortcut of rvo_vel_body (its comment has the proof): one cos per neighbour decides the candidates away from
-      // the rounding tie, the rest take the reference's own sequence
+      // the shortcut of rvo_neighbours (its comment has the proof): one cos per neighbour decides the candidates away
+      // from the rounding tie, the rest take the reference's own sequence
       const double thr = cos((alpha_c - 0.5) / 100.0);
       const double thr2n = thr * thr * dot3b(ax, ay, az, ax, ay, az);
       const double nab2 = dot3b(ax, ay, az, ax, ay, az);

@@ -373,6 +373,57 @@ def test_hip_rvo_vel_matches_oracle_where_cs_is_one():
     _gpu_compare("rvo_vel/cs_is_one", edge_state(), edge_oracle(), V2, EDGE_ACCELER)
 
 
+def _city_drone_side_cases():
+    """The cs = 1 edge scene, eight_waves (64 live candidates: mask bit 63) and the smallest scene of the table whose
+    floors include IN_ONLY."""
+    with_in_only = [k for k, sc in enumerate(SCENES) if IN_ONLY in sc.floors]
+    small = min(with_in_only, key=lambda k: SCENES[k].E * SCENES[k].N)
+    k8 = SCENE_IDS.index("eight_waves")
+    assert small != k8
+    return [("cs_is_one", None), ("eight_waves", k8), (SCENES[small].label, small)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("label,k", _city_drone_side_cases(), ids=[c[0] for c in _city_drone_side_cases()])
+def test_hip_rvo_vel_city_drone_side_is_rvo_vel_on_the_pinned_states(label, k):
+    """rvo_vel_city with a reach no building is within (1e-300) on the states the oracle pins for rvo_vel: the row is
+    rvo_vel's bit for bit, nothing is gated or blocked, and the tier is the oracle's branch - 1 for a winner outside
+    every cone, 2 for one inside, 4 for no live candidate - for every agent further than 1e-9 from a rounding tie;
+    those nearer are at most knife_bound of them."""
+    import torch
+    from rvo3d_amd import BatchedDroneEnv
+    if k is None:
+        state, run, vmax, acceler = edge_state(), edge_oracle(), V2, EDGE_ACCELER
+    else:
+        state, run, vmax, acceler = scene_state(k), scene_oracle(k), SCENES[k].vmax, SCENES[k].acceler
+    w, pos, vel, radius, priority = state
+    E, N = pos.shape[:2]
+    env = BatchedDroneEnv(w, neighbors_num=10, radius=radius, priority=priority)
+    try:
+        env.set_state(pos=pos, vel=vel)
+        plain = env.rvo_vel(vmax, acceler)
+        city, diag = env.rvo_vel_city(diagnostics=True, vmax=vmax, acceler=acceler, reach=1e-300)
+        torch.cuda.synchronize()
+        assert torch.equal(city.view(torch.int64), plain.view(torch.int64))
+        d = {n: t.cpu().numpy() for n, t in diag.items()}
+    finally:
+        env.close()
+    assert not d["n_gated"].any()
+    assert not d["blocked_mask"].any()
+    if label == "eight_waves":
+        assert (d["live_mask"] < 0).any()                                     # bit 63 of the int64 view
+    sure = run.margin >= 1e-9
+    print(label, "agents", E * N, "within 1e-9 of a tie", int((~sure).sum()),
+          "tiers", {t: int((d["tier"] == t).sum()) for t in (0, 1, 2, 3, 4)})
+    assert int((~sure).sum()) <= knife_bound(E * N)
+    want = np.zeros((E, N), np.int32)
+    want[(run.branch == OUT_ONLY) | (run.branch == OUT_SOME_IN)] = 1
+    want[run.branch == IN_ONLY] = 2
+    want[run.branch == NONE] = 4
+    assert (want > 0).all()
+    assert (d["tier"][sure] == want[sure]).all(), np.argwhere(sure & (d["tier"] != want))[:10]
+
+
 @pytest.mark.gpu
 def test_hip_rvo_vel_rejects_bad_arguments_and_writes_nothing():
     import ctypes as C
