@@ -6,7 +6,22 @@ rvo3d_rvo_vel where no building passes the gate (rule 5); planted drones; the ar
 Shapes (CASES): N 5 / 64 / 65 / 130 - part of a wave, a full wave, the wave seam, three waves; E 3..6; nb_max 0 (the empty
 shared list), 1, 3 and T + 1 = 129 at N = 65 (two tiles); per-env sets with unequal counts, one of them 0, and fillers; the
 shared list; a counted handle with ghost rows; acceler 0, 0.5 and 1 (64 candidates); one vmax component 0; patrols with
-static, arriving and cruising records, advanced MOVES times through rvo3d_move_env_buildings."""
+static, arriving and cruising records, advanced MOVES times through rvo3d_move_env_buildings.
+
+The second pass of rvo_city_body - the workgroup-wide vote, the lanes that wait at load_tile's barriers, the tb[4] minima
+carried across tiles - has a scene of its own (moving_city_case.second_pass_scene: a counted handle, N 130, nb_max 193 =
+T + 1 at T = 192, acceler 1).  The restatement on the CPU (tests/test_moving_city_host.py) gives there, and the test
+asserts from the restatement of the device's own masks:
+
+    tier-3 lanes   two distinct tb   ... at lane >= 64   least tb from record 192   first tile alone differs   mixed envs
+    137            36                21 (>= 10)          2 (>= 1)                   2 (>= 1)                   1 (>= 1)
+
+"least tb from record 192": the winning candidate's minimum over the buildings comes from the one record of the second
+tile; "first tile alone differs": the lane's velocity is another one when tb is taken from records 0 .. 191 only - what a
+second pass that read only the first tile would write, so such a kernel fails the bit-for-bit comparison (tried once: a
+library built that way fails this test and passes every one of the CASES); "mixed envs": a wave without a tier-3 lane
+beside one with (env 1's first wave flies over every roof).  Two of the CASES assert floors of their own tier-3 figures
+(119 lanes, 16 of them with two distinct tb, at the wave seam; 12 lanes at three waves)."""
 import ctypes as C
 import functools
 import types
@@ -17,6 +32,7 @@ import torch
 
 from rvo3d_amd import BatchedDroneEnv, BuildingMotion, World, _lib
 import building_rows_moving_ref as ref8
+import moving_city_case as mc
 import rvo_city_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +51,8 @@ CASES = [
     (4, 5, 0, 1.0, (2.0, 2.0, 2.0), None, "no buildings at all"),
 ]
 IDS = [c[-1] for c in CASES]
+# floors of (tier-3 lanes, those whose blocked candidates have at least two distinct tb); the CPU counts 119 / 16 and 12 / 0
+TIER3_FLOORS = {"the wave seam, two tiles": (60, 8), "three waves": (6, 0)}
 
 
 def routes(E, N):
@@ -132,6 +150,10 @@ def test_device_equals_the_restatement_bit_for_bit(E, N, nb_max, acceler, vmax, 
     assert np.array_equal(bits(out.cpu().numpy()), bits(want["out_vel"]))
     tier = want["tier"]
     assert (tier[live] >= 1).all() and (tier[~live] == 0).all()
+    if what in TIER3_FLOORS:   # the second pass is exercised: tier-3 lanes, and lanes whose candidates hit at different times
+        lanes, two = TIER3_FLOORS[what]
+        assert int((tier == 3).sum()) >= lanes, int((tier == 3).sum())
+        assert two == 0 or mc.distinct_tb_lanes(sc, bld, mot, tier, u64(diag["live_mask"]), kw) >= two
     for k in diag:                                                           # rule 4: ghost rows are zeros
         assert not diag[k].cpu().numpy()[~live].any(), k
     assert not out.cpu().numpy()[~live].any()
@@ -152,6 +174,36 @@ def test_device_equals_the_restatement_bit_for_bit(E, N, nb_max, acceler, vmax, 
     assert torch.equal(out0.view(torch.int64), plain.view(torch.int64))      # rule 5
     t0 = diag0["tier"].cpu().numpy()
     assert np.isin(t0[live], [1, 2, 4]).all()
+
+
+def test_the_second_pass_across_waves_and_tiles():
+    """moving_city_case.second_pass_scene, bit for bit against the restatement, and the figures of the module docstring
+    from the restatement's output: tier-3 lanes beyond the first wave with distinct tb, a winner decided by the record of
+    the second tile, and an env in which one wave needs no second pass while the others do."""
+    sc = mc.second_pass_scene()
+    assert (sc.N, sc.bld0.shape[1], mc.PASS_MOVES) == (130, 193, MOVES) and MAP == mc.PASS_MAP
+    env, motion = live_env(sc)
+    assert "counted" in env.kernel_name()
+    bld, mot = now(sc, motion)
+    b_ref, leg_ref = mc.second_pass_now()
+    assert np.array_equal(bits(bld), bits(b_ref)) and np.array_equal(mot[2], leg_ref)
+    kw = mc.PASS_KW
+    out, diag = env.rvo_vel_city(diagnostics=True, **kw)
+    want = restate(sc, env, diag, bld, mot, **kw)
+    live = np.arange(sc.N)[None, :] < sc.drone_counts[:, None]
+    assert np.array_equal(u64(diag["live_mask"]), want["live_mask"])
+    assert np.array_equal(u64(diag["blocked_mask"]), want["blocked_mask"])
+    assert np.array_equal(diag["n_gated"].cpu().numpy(), want["n_gated"])
+    assert np.array_equal(diag["tier"].cpu().numpy(), want["tier"])
+    assert np.array_equal(bits(out.cpu().numpy()), bits(want["out_vel"]))
+    for k in diag:
+        assert not diag[k].cpu().numpy()[~live].any(), k
+    assert not out.cpu().numpy()[~live].any()
+    assert (want["n_gated"][1, :64] == 0).all() and (want["n_gated"][0, :sc.drone_counts[0]] > 0).all()
+    fig = mc.second_pass_figures(sc, bld, mot[2], want["tier"], u64(diag["live_mask"]), env.des_vel().cpu().numpy())
+    print(fig)
+    assert fig["distinct_64"] >= 10 and fig["from_192"] >= 1 and fig["mixed_envs"] >= 1, fig
+    assert fig["first_tile_differs"] >= 1, fig
 
 
 def raw(env, out, motion="attached", dt=DT, diag=None, **kw):
