@@ -29,7 +29,9 @@ static long g_checks = 0;
 static const int kN[] = {1, 5, 8, 16, 22, 32, 40, 63, 64, 65, 100, 128, 129, 192, 200, 256, 257, 300, 512};
 static const int kNm[] = {0, 1, 3, 5, 10, 12};
 static const int kE[] = {1, 3, 4096};
-static const double kMaps[4][3] = {{10, 10, 5}, {100, 80, 10}, {500, 500, 10}, {2000, 2000, 50}};
+static const double kMaps[][3] = {{10, 10, 5}, {100, 80, 10}, {500, 500, 10}, {2000, 2000, 50}, {6000, 300, 30},
+                                  {8000, 8000, 50}};
+static const int kNumMaps = (int)(sizeof(kMaps) / sizeof(kMaps[0]));
 static const char* const kLdsMsg = "neighbors_num * num_drones needs more than 160 KiB of LDS";
 
 static rvo3d_config config(int E, int N, int nm, const double* map, int nb = 0, int max_points = 4) {
@@ -56,7 +58,9 @@ static void check_thresholds() {
   }
 }
 
-// b. the float32 squared distance of a pair at most 10.5 m apart, both within cmax of the centre, is within band / 2
+// b. the float32 squared distance of a pair at most 10.5 m apart, both within cmax of the centre, is within band / 2,
+//    and its float32 v . rel (the fma chain of x1_pairs, v cast to float as stage_f32 casts it) within half of the
+//    drone's kd = kdot |v|_1
 static void check_bands(const double* map, const Params& P, const Cold& C) {
   REQUIRE(P.T10 == sq_threshold(10.0) && C.T5 == sq_threshold(5.0) && C.T04 == sq_threshold(0.4), "thresholds");
   REQUIRE(P.t10n < -(float)P.T10, "t10n %a", P.t10n);
@@ -66,11 +70,11 @@ static void check_bands(const double* map, const Params& P, const Cold& C) {
   REQUIRE(P.x1_gap == 512.0f * std::nextafter(P.band, 0.0f), "x1_gap %a band %a", P.x1_gap, P.band);
   REQUIRE(P.band > 0.0f && C.kdot > 0.0f && P.x1_cs2 > 0.0f, "positive bands");
   for (int k = 0; k < 3; ++k) REQUIRE(C.cen[k] == 0.5 * map[k], "cen");
-  Rng r(0x5eed0000u + (uint64_t)map[0]);
+  Rng r(0x5eed0000u + (uint64_t)map[0] + (uint64_t)map[1]);
   const double cm = (double)C.cmax * 0.999999;
-  double worst = 0.0;
+  double worst = 0.0, worst_dot = 0.0;
   for (int it = 0; it < 2000000; ++it) {
-    double a[3], b[3], off[3], n2 = 0.0;
+    double a[3], b[3], off[3], v[3], n2 = 0.0;
     for (int k = 0; k < 3; ++k) {
       const double mag = (it & 1) ? r.uni(0.5 * cm, cm) : r.uni(0.0, cm);  // half of them far out: the largest rounding
       a[k] = r.below(2) ? mag : -mag;
@@ -79,9 +83,12 @@ static void check_bands(const double* map, const Params& P, const Cold& C) {
     }
     const double len = (it & 2) ? r.uni(10.0, 10.499) : r.uni(0.0, 10.499);
     const double sc = n2 > 0.0 ? len / std::sqrt(n2) : 0.0;
-    float d[3];
-    double d2 = 0.0;
+    float d[3], fv[3];
+    double d2 = 0.0, dotp = 0.0;
+    const double vscale = (it & 4) ? 10.0 : 1.0;  // |v|_1 of order 1 and of order 10
     for (int k = 0; k < 3; ++k) {
+      v[k] = vscale * r.uni(-1.0, 1.0);
+      fv[k] = (float)v[k];
       b[k] = a[k] + off[k] * sc;
       if (std::fabs(b[k]) > cm) b[k] = a[k] - off[k] * sc;  // (cmax >= 16 > 10.5: this one is inside)
       const double xa = C.cen[k] + a[k], xb = C.cen[k] + b[k];  // the coordinates as the state holds them
@@ -89,13 +96,20 @@ static void check_bands(const double* map, const Params& P, const Cold& C) {
       REQUIRE(std::fabs(ca) <= (double)C.cmax && std::fabs(cb) <= (double)C.cmax, "sample outside cmax");
       d[k] = (float)ca - (float)cb;
       d2 += (xa - xb) * (xa - xb);
+      dotp += v[k] * (xa - xb);
     }
     REQUIRE(d2 <= 10.5 * 10.5, "sample too far apart: %g", d2);
     const float d2f = std::fma(d[2], d[2], std::fma(d[1], d[1], d[0] * d[0]));
     const double e = std::fabs((double)d2f - d2);
     if (e > worst) worst = e;
     REQUIRE(e <= 0.5 * (double)P.band, "map %g: fp32 d2 off by %g, band %g", map[0], e, (double)P.band);
+    const float dotf = std::fma(fv[2], d[2], std::fma(fv[1], d[1], fv[0] * d[0]));
+    const double kd = (double)C.kdot * ((double)std::fabs(fv[0]) + (double)std::fabs(fv[1]) + (double)std::fabs(fv[2]));
+    const double ed = std::fabs((double)dotf - dotp);
+    if (kd > 0.0 && ed / kd > worst_dot) worst_dot = ed / kd;
+    REQUIRE(ed <= 0.5 * kd, "map %g: fp32 v.rel off by %g, kd %g", map[0], ed, kd);
   }
+  std::printf("kdot: map %g x %g x %g  worst |v.rel f32 - v.rel| = %.3f x kd\n", map[0], map[1], map[2], worst_dot);
   std::printf("band: map %g x %g x %g  worst |d2f - d2| = %.3f x band\n", map[0], map[1], map[2], worst / (double)P.band);
 }
 
@@ -149,7 +163,7 @@ static void check_geometry(const rvo3d_config& c, const Params& P, const Geometr
 
 static void check_matrix() {
   int shapes = 0;
-  for (int mi = 0; mi < 4; ++mi) {
+  for (int mi = 0; mi < kNumMaps; ++mi) {
     bool bands_done = false;
     for (int N : kN) for (int nm : kNm) for (int E : kE) {
       const rvo3d_config c = config(E, N, nm, kMaps[mi]);
