@@ -80,6 +80,10 @@ struct rvo3d_env {
   // rvo3d_eval_account_safety: the scan's per-env step values, [E] doubles x 3 then [E] int32; allocated by the first
   // rvo3d_load_world and kept until rvo3d_destroy
   double* safety_scratch = nullptr;
+  // rvo3d_orca_vel: the lanes' planes, [slot][6][E * N] doubles; allocated by the first call, grown by a call that needs
+  // more slots (max_neighbors + max_buildings) and kept until rvo3d_destroy
+  double* orca_ws = nullptr;
+  size_t orca_ws_bytes = 0;
 };
 
 namespace {
@@ -513,6 +517,7 @@ int rvo3d_destroy(rvo3d_env* h) {
   if (h->env_bld) (void)hipFree(h->env_bld);
   if (h->counts_dev) (void)hipFree(h->counts_dev);
   if (h->safety_scratch) (void)hipFree(h->safety_scratch);
+  if (h->orca_ws) (void)hipFree(h->orca_ws);
   if (h->arena) (void)hipFree(h->arena);
   delete h;
   return RVO3D_OK;
@@ -1539,6 +1544,54 @@ int rvo3d_rvo_vel_city(rvo3d_env* h, const rvo3d_rvo_city_args* a, const rvo3d_b
   hipLaunchKernelGGL(h->counted ? rvo3d::rvo_city_counted_kernel : rvo3d::rvo_city_kernel, dim3((unsigned)h->P.E),
                      dim3((unsigned)T), (size_t)T * 8 * sizeof(double), static_cast<hipStream_t>(stream), h->P, A, Y,
                      building_vel_args(m, dt));
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_orca_vel(rvo3d_env* h, const rvo3d_orca_args* a, const rvo3d_building_motion* m, double dt, void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  const char* why = "";
+  if (int rc = rvo3d::orca_check(a, h->env_bld != nullptr, m, dt, &why)) return fail(rc, why);
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const size_t EN = (size_t)h->P.E * h->P.N;
+  const size_t need = (size_t)rvo3d::orca_ws_slots(a->max_neighbors, a->max_buildings) * 6 * EN * sizeof(double);
+  if (need > h->orca_ws_bytes) {  // (hipFree waits for the launches that still read the old one)
+    if (h->orca_ws) (void)hipFree(h->orca_ws);
+    h->orca_ws = nullptr;
+    h->orca_ws_bytes = 0;
+    HIP_TRY(hipMalloc((void**)&h->orca_ws, need));
+    h->orca_ws_bytes = need;
+  }
+  const rvo3d::OrcaArgs Y{a->time_horizon, a->time_step, a->max_speed, a->pref_speed, a->neighbor_dist * a->neighbor_dist,
+                          a->reach, a->below, a->clear_xy, a->max_neighbors, a->max_buildings, a->out_vel,
+                          a->n_neighbors, a->n_buildings, a->status, a->slack, h->orca_ws, EN};
+  const int T = (int)align_up((size_t)h->P.N, 64);
+  hipLaunchKernelGGL(h->counted ? rvo3d::orca_counted_kernel : rvo3d::orca_kernel, dim3((unsigned)h->P.E),
+                     dim3((unsigned)T), rvo3d::orca_lds_bytes(T), static_cast<hipStream_t>(stream), h->P, Y,
+                     building_vel_args(m, dt));
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
+int rvo3d_vel_command(rvo3d_env* h, const double* vel, double* action, uint8_t* clipped, void* stream) {
+  RVO3D_API_BEGIN
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  if (!vel || !action) return fail(RVO3D_ERR_INVALID, "vel / action are required");
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const size_t EN = (size_t)h->P.E * h->P.N;
+  hipLaunchKernelGGL(h->counted ? rvo3d::vel_command_counted_kernel : rvo3d::vel_command_kernel,
+                     dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), h->P, vel, action,
+                     clipped);
   HIP_TRY(hipGetLastError());
   return RVO3D_OK;
   RVO3D_API_END

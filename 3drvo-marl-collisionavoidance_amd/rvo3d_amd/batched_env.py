@@ -490,6 +490,52 @@ class BatchedDroneEnv:
         _lib.check(_lib.lib().rvo3d_rvo_vel_city(self._h, C.byref(a), m, dt, self._stream()), "rvo3d_rvo_vel_city")
         return (out, diag) if diagnostics else out
 
+    def orca_vel(self, time_horizon: float = 5.0, time_step: float = 1.0, max_speed: float = 2.0, pref_speed: float = 1.0,
+                 neighbor_dist: float = 10.0, max_neighbors: int = 10, max_buildings: int = 4, reach: float = 10.0,
+                 below: float = 1.0, clear_xy: float = 0.0, diagnostics: bool = False):
+        """The ORCA velocity of every drone (rvo3d_orca_vel; the rules are in include/rvo3d.h): one half-space of
+        permitted velocities per kept neighbour (the `max_neighbors` nearest within `neighbor_dist`, each drone taking
+        half of the avoidance) and per kept building (the `max_buildings` of least gap among those that pass the gate
+        `reach` / `below`, as upright cylinders of unlimited height widened by `clear_xy`, taking no share), and the
+        velocity nearest pref_speed * des_vel inside them and the ball of `max_speed`, by the published linear programs.
+        Collision-free for `time_horizon` when every drone flies its result - which needs velocity_command: a velocity
+        handed to step() as it is is read as an action.  The buildings are the per-env sets while sets are attached, else
+        the world's shared list; the motion attached now (attach_building_motion) is picked up at every call.  Returns
+        [E, N, 3] float64; with diagnostics=True also a dict of n_neighbors, n_buildings, status (int32; 0 ghost, 1 the
+        preferred velocity was feasible, 2 solved by the program, 3 infeasible: the fallback's least penetration) and
+        slack (float64: the largest penetration of a drone plane, 0 unless status 3), [E, N] each.  One launch, no
+        synchronisation, behind a first call that allocates the handle's plane workspace."""
+        out = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
+        diag = {}
+        names = ("n_neighbors", "n_buildings", "status", "slack")
+        if diagnostics:
+            for name in names:
+                diag[name] = torch.empty((self.E, self.N), dtype=torch.float64 if name == "slack" else torch.int32,
+                                         device=self.device)
+        a = _lib.OrcaArgs(float(time_horizon), float(time_step), float(max_speed), float(pref_speed), float(neighbor_dist),
+                          int(max_neighbors), int(max_buildings), float(reach), float(below), float(clear_xy),
+                          out.data_ptr(), *[diag[n].data_ptr() if diagnostics else None for n in names])
+        m, dt = self._motion_args()
+        _lib.check(_lib.lib().rvo3d_orca_vel(self._h, C.byref(a), m, dt, self._stream()), "rvo3d_orca_vel")
+        return (out, diag) if diagnostics else out
+
+    def velocity_command(self, vel, return_clipped: bool = False):
+        """The action that makes the next step() fly the velocity `vel` [E, N, 3] (rvo3d_vel_command; the formulas are in
+        include/rvo3d.h): speed change, yaw and pitch increments from the current velocity and heading, each clipped to
+        [-1, 1] as the step would clip it.  Returns [E, N, 3] float64, with return_clipped=True also uint8 [E, N]: bit k set
+        where component k was clipped (the step then does not reach `vel`).  Ghost rows are zero.
+        On a handle with action_decimals >= 0 the command is quantised like any action; evaluation envs use -1.  The
+        step's RVO reward and VO rows still read the action as if it were a velocity (quirk Q3): that does not matter to
+        success, length, speed or the safety figures."""
+        w = torch.as_tensor(vel, device=self.device).to(torch.float64).contiguous()
+        if tuple(w.shape) != (self.E, self.N, 3):
+            raise ValueError(f"vel must be [{self.E}, {self.N}, 3], not {tuple(w.shape)}")
+        out = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
+        clipped = torch.empty((self.E, self.N), dtype=torch.uint8, device=self.device) if return_clipped else None
+        _lib.check(_lib.lib().rvo3d_vel_command(self._h, _ptr(w), _ptr(out), None if clipped is None else _ptr(clipped),
+                                                self._stream()), "rvo3d_vel_command")
+        return (out, clipped) if return_clipped else out
+
     # -- state ------------------------------------------------------------------------
     def get_state(self):
         E, N, dev = self.E, self.N, self.device

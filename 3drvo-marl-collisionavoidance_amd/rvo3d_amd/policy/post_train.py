@@ -91,13 +91,19 @@ def summarize_records(step, env, length, ret, speed, flags, policy_name="policy"
 class post_train:
     def __init__(self, env, num_episodes=100, max_ep_len=150, acceler_vel=1.0, render=False,
                  save=False, neighbor_region=4, neighbor_num=5, args=None, fused=False, policy_kernel=None,
-                 poll_every=8, seed=0, safety=False, near_margin=0.5, rvo=None, **kwargs):
+                 poll_every=8, seed=0, safety=False, near_margin=0.5, rvo=None, command="raw", **kwargs):
         """fused: the device-side loop (module docstring); policy_kernel: None (policy.step_tensors) or the
         KernelPolicyStep kind that runs the policy - "mlp", "mlp_x3" (the MLP actor-critic, bf16 / float32-class),
         "rnn_tiles" or "rnn_tiles_x3" (the biGRU actor-critic, likewise) - either loop; poll_every: steps between two host
         reads of the fused loop; seed: of the kernels' counter-based noise; safety / near_margin: the safety figures (module
         docstring), off by default: neither loop then makes a launch it did not make before; rvo: keyword arguments of the
-        classical controller policy_test flies for policy_type "rvo" (env.rvo_vel) and "rvo_city" (env.rvo_vel_city)."""
+        classical controller policy_test flies for policy_type "rvo" (env.rvo_vel), "rvo_city" (env.rvo_vel_city) and
+        "orca" (env.orca_vel); command: what becomes of the controller's velocity (policy types without a network) - "raw":
+        handed to env.step as it is, which reads it as acceleration, yaw and pitch increments (the reference's glue);
+        "velocity": through env.velocity_command first, so that the step flies that velocity."""
+        if command not in ("raw", "velocity"):
+            raise ValueError(f"command must be 'raw' or 'velocity', not {command!r}")
+        self.command = command
         if policy_kernel not in (None, "mlp", "mlp_x3", "rnn_tiles", "rnn_tiles_x3"):
             raise ValueError("policy_kernel must be None, 'mlp', 'mlp_x3', 'rnn_tiles' or 'rnn_tiles_x3', "
                              f"not {policy_kernel!r}")
@@ -167,14 +173,21 @@ class post_train:
 
     # -- evaluation -------------------------------------------------------------------------
     def _classical(self, policy_type):
-        """What both loops fly without a network: "rvo" - env.rvo_vel, "rvo_city" - env.rvo_vel_city, each with the
-        constructor's rvo= parameters; any other policy_type - env.des_vel."""
+        """What both loops fly without a network: "rvo" - env.rvo_vel, "rvo_city" - env.rvo_vel_city, "orca" -
+        env.orca_vel, each with the constructor's rvo= parameters; any other policy_type - env.des_vel."""
         env = self.env
         if policy_type == "rvo":
             return lambda: env.rvo_vel(**self.rvo)
         if policy_type == "rvo_city":
             return lambda: env.rvo_vel_city(**self.rvo)
+        if policy_type == "orca":
+            return lambda: env.orca_vel(**self.rvo)
         return env.des_vel
+
+    def _action(self):
+        """The action of a step without a network: _fly()'s velocity, by the constructor's command=."""
+        v = self._fly()
+        return self.env.velocity_command(v) if self.command == "velocity" else v
 
     def policy_test(self, policy_type="drl", policy_path=None, policy_name="policy", result_path=None,
                     result_name="/result.txt", policy=None, policy_dict=False, **_unused):
@@ -216,7 +229,7 @@ class post_train:
                 vel = env.vel                                              # [E, N, 3] float64
                 action = (torch.as_tensor(self.acceler_vel, dtype=torch.float32, device=dev) * a_inc).double() + vel
             else:
-                action = self._fly()
+                action = self._action()
             obs, cnt, rew, done, info, fin = env.step(action)             # plain drone_step
             if ghost is None:
                 speed_sum += torch.linalg.vector_norm(env.vel, dim=-1).mean(dim=1)
@@ -315,7 +328,7 @@ class post_train:
                 a = act_fn(obs.view(-1, env.W), cnt.view(-1)).view(E, N, 3)
                 action = env.eval_action(a, self.acceler_vel)
             else:
-                action = self._fly()
+                action = self._action()
             obs, cnt, rew, done, info, fin = env.step(action)             # plain drone_step
             if self.with_safety:
                 _lib.check(L.rvo3d_eval_account_safety(env._h, p(rew), p(done), p(info), p(fin), self.max_ep_len, quota,

@@ -836,6 +836,91 @@ typedef struct rvo3d_rvo_city_args {
 int rvo3d_rvo_vel_city(rvo3d_env *h, const rvo3d_rvo_city_args *args,
                        const rvo3d_building_motion *motion, double dt, void *stream);
 
+/* The ORCA velocity of every drone on the current state: van den Berg, Guy, Lin, Manocha, "Reciprocal n-body collision
+ * avoidance" in three dimensions - one half-space of permitted velocities per neighbour and per building, and the
+ * velocity nearest the preferred one in their intersection, by the authors' incremental linear programs.  When every
+ * drone applies its result the drones do not collide for time_horizon.  Nothing of this is in the reference; the rules
+ * are the published algorithm's, restated in tests/orca_ref.py.  motion, dt: as for rvo3d_rvo_vel_city.
+ * The result is defined by these rules, to the last bit; every value is a float64, every operation rounded on its own (no
+ * FMA), a square is x * x, a . b = (a_x*b_x + a_y*b_y) + a_z*b_z, |a| = sqrt(a . a), a x b the usual cross product, sqrt
+ * and / are correctly rounded, a vector is divided by a scalar component by component.
+ *   1. Preferred velocity.  pref = pref_speed * des, des the des_vel rvo3d_rvo_vel uses.
+ *   2. Neighbours.  The other drones j of the env (on a counted handle: its live ones) with rel = p_j - p_i and
+ *      d2 = rel . rel < neighbor_dist * neighbor_dist; the max_neighbors with the least (d2, j) are kept, in that order.
+ *      Priorities are not used: every drone takes half.  n_neighbors is the number kept.
+ *   3. Buildings.  Env e's buildings as in rule 1 of rvo3d_rvo_vel_city, with its gate (h_b > p_z - below and d <= reach)
+ *      and its velocity vb.  The max_buildings with the least (gap, index) are kept, gap = d - (r + r_b), in that order;
+ *      n_buildings is the number kept.  A building is an upright cylinder of unlimited height that takes no share:
+ *      rel = (x_b - p_x, y_b - p_y, 0), w_rel = (v_x - vb_x, v_y - vb_y, 0), R = (r + r_b) + clear_xy.  Its plane's
+ *      normal is planar: it constrains (v_x, v_y) only.  A drone that is above a roof by less than `below` is therefore
+ *      treated as beside that cylinder, not over it: it is pushed out sideways.
+ *   4. The plane of an agent (rel, w_rel = v_i - v_j, R; share 0.5 for a drone, 1 for a building), tau = time_horizon:
+ *        d2 > R*R:  w = w_rel - rel / tau, dp = w . rel.
+ *          dp < 0 and dp*dp > (R*R) * (w . w) (the cut-off circle):  n = w / |w|, u = (R / tau - |w|) n.
+ *          else (a leg):  a = d2, b = rel . w_rel, cr = rel x w_rel, c = w_rel . w_rel - (cr . cr) / (d2 - R*R),
+ *            t = (b + sqrt(max(b*b - a*c, 0))) / a, ww = w_rel - t rel, n = ww / |ww|, u = (R*t - |ww|) n.
+ *        d2 <= R*R (overlapping now):  w = w_rel - rel / time_step, n = w / |w|, u = (R / time_step - |w|) n.
+ *      point = v_i + share * u; the half-space is n . (v - point) >= 0.  Guards: max(x, 0) is x > 0 ? x : 0 (0 for a NaN);
+ *      a zero-length w takes n = (1, 0, 0).  A zero-length ww - w_rel exactly on the cone's axis, two drones exactly
+ *      head-on - is where the published quotient is 0 / 0 and every normal of the cone round its axis is equally near;
+ *      (1, 0, 0) for both drones would move both the same way and avoid nothing, so the normal towards perp = e x rel
+ *      is taken, e = (0, 0, 1), or (1, 0, 0) when rel_x = rel_y = 0:
+ *        n = (sqrt(d2 - R*R) / |rel|) (perp / |perp|) - (R / |rel|) (rel / |rel|),
+ *      the limit of ww / |ww| from that side.  The other drone, with -rel, takes -n, as reciprocity needs, and a planar
+ *      pair stays planar.  The published library multiplies by 1 / tau where this divides by tau.
+ *      No NaN arises for finite state whose squares neither overflow nor underflow to the point that
+ *      (cr . cr) / (d2 - R*R) overflows.
+ *   5. Order.  Building planes first, by ascending (gap, index), then drone planes by ascending (d2, j).
+ *   6. The program: the authors' four (on a line, on a plane, in space, and the fallback that minimises the largest
+ *      penetration when the planes have no common point), EPS = 1e-5, for the point of the ball |v| <= max_speed nearest
+ *      pref; csrc/rvo3d_orca_rules.hpp is the statement, operation for operation.  Beyond the published text: a point
+ *      projected onto a plane that coincides with the plane circle's centre stays there; on a line the discriminant
+ *      test is !(disc >= 0).  In the fallback the building planes are hard, as the authors' 2-D library treats obstacle
+ *      lines: they enter every projected problem unchanged, only drone planes are relaxed.  When the building planes
+ *      themselves have no common point in the ball (max_speed too small to get away from a moving building, a drone
+ *      inside two clearance disks) the program fails at a building plane; that plane is then relaxed like a drone's, the
+ *      building planes before it stay hard.
+ *      status: 1 - pref, clipped to the ball, satisfies every plane and is the result; 2 - solved by the program;
+ *      3 - no common point, the fallback's result.  slack: for status 3 the largest n . (point - v) over the drone
+ *      planes at the result, not below 0; 0 for status 1 and 2.
+ *   7. Ghost rows (counted handle, d >= counts[e]): out_vel 0 and every diagnostic 0 (status 0); the ghost's state is not
+ *      read.
+ * One workgroup per env, one lane per drone; a lane's planes live in a workspace the handle owns ([slot][6][E * N]
+ * doubles, 2 * (max_neighbors + max_buildings) - 1 slots), allocated by the first call and grown by a call that needs
+ * more: such a call allocates (and a growing one waits for the device), every other one is one launch without
+ * allocation, synchronisation or atomics.  Calls on one handle must not overlap on different streams.
+ * Every argument check runs before the first HIP call and a refused call writes nothing: RVO3D_ERR_STATE without a loaded
+ * world, or for a motion without attached per-env sets; RVO3D_ERR_INVALID for a null args / out_vel / pointer inside
+ * motion, for each non-finite or out-of-range double, for max_neighbors outside 1..16, max_buildings outside 0..8, and
+ * for dt not finite or < 0 (checked with and without a motion). */
+typedef struct rvo3d_orca_args {
+  double time_horizon;                     /* finite > 0: tau                                              */
+  double time_step;                        /* finite > 0: the step overlapping agents separate in (the env's: 1) */
+  double max_speed, pref_speed;            /* finite >= 0                                                  */
+  double neighbor_dist;                    /* finite > 0                                                   */
+  int32_t max_neighbors, max_buildings;    /* 1..16, 0..8                                                  */
+  double reach, below;                     /* building gate, finite > 0 / finite >= 0                      */
+  double clear_xy;                         /* finite >= 0: extra clearance round the cylinder              */
+  double *out_vel;                         /* DEVICE [E][N][3], required                                   */
+  /* DEVICE [E][N], each nullable */
+  int32_t *n_neighbors, *n_buildings, *status;
+  double *slack;
+} rvo3d_orca_args;
+int rvo3d_orca_vel(rvo3d_env *h, const rvo3d_orca_args *args,
+                   const rvo3d_building_motion *motion, double dt, void *stream);
+
+/* The action whose kinematic step (drone.kinematicstep: rvo3d_step*) turns the handle's current velocity and heading
+ * into the wanted velocity w = vel [E][N][3] f64 (DEVICE): action [E][N][3] f64 (DEVICE, may be vel itself),
+ *   a0 = |w| - |v|,  a1 = wrap180(atan2(w_y, w_x) deg - yaw) / 90,  a2 = (asin(clamp(w_z / |w|, -1, 1)) deg - pitch) / 90,
+ * |x| = sqrt((x_x*x_x + x_y*x_y) + x_z*x_z), deg = * 57.29577951308232, wrap180(t) = t - 360 * floor((t + 180) / 360);
+ * |w| = 0 keeps both angles (a1 = a2 = 0).  Each component is then clipped to [-1, 1], as the step would clip it;
+ * clipped (DEVICE [E][N] bytes, nullable): bit k set where component k needed it - the step then does not reach w.
+ * Ghost rows (counted handle): zeros.  A finished drone is parked by the step whatever its action.  On a handle with
+ * action_decimals >= 0 the step quantises the command like any action.  atan2 and asin are the device library's:
+ * results agree with a host evaluation to a few ulp, not to the bit.  One launch, no synchronisation.
+ * RVO3D_ERR_STATE without a loaded world, RVO3D_ERR_INVALID for a null vel / action. */
+int rvo3d_vel_command(rvo3d_env *h, const double *vel, double *action, uint8_t *clipped, void *stream);
+
 /* Zero-copy views of the state arrays, READ-ONLY: the step keeps values derived from the
  * state on file between calls (des_vel, the in-range words of the pair gate, the current /
  * previous waypoint); state is changed through rvo3d_set_state / rvo3d_reset*, which bring

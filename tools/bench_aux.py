@@ -106,6 +106,9 @@ timed("reset_drones (1/7 of the drones) + observe", lambda i: (env.reset_drones(
 timed("des_vel (cal_des_list)", lambda i: env.des_vel(), 48 + 24)
 timed("rvo_vel (classical RVO velocity selection)", lambda i: env.rvo_vel(vmax=(2.0, 2.0, 2.0), acceler=0.5))
 timed("rvo_vel_city (this world has no buildings)", lambda i: env.rvo_vel_city(vmax=(2.0, 2.0, 2.0), acceler=0.5))
+timed("orca_vel (this world has no buildings)", lambda i: env.orca_vel())
+want = env.des_vel()
+timed("velocity_command (velocity -> action)", lambda i: env.velocity_command(want), 64 + 24 + 24)
 flags = env.error_flags()
 print("device error word", flags)
 
