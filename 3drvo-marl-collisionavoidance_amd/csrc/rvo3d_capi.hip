@@ -1580,6 +1580,38 @@ int rvo3d_orca_vel(rvo3d_env* h, const rvo3d_orca_args* a, const rvo3d_building_
   RVO3D_API_END
 }
 
+int rvo3d_shield_action(rvo3d_env* h, const rvo3d_shield_args* a, const rvo3d_building_motion* m, double dt, void* stream) {
+  RVO3D_API_BEGIN
+  // every argument check before the first HIP call
+  if (!h) return fail(RVO3D_ERR_INVALID, "null handle");
+  if (!h->world_loaded) return fail(RVO3D_ERR_STATE, "rvo3d_load_world has not been called");
+  const char* why = "";
+  if (int rc = rvo3d::shield_check(a, h->env_bld != nullptr, m, dt, &why)) return fail(rc, why);
+  DeviceGuard dg;
+  int rc = check(h, true, dg);
+  if (rc) return rc;
+  const size_t EN = (size_t)h->P.E * h->P.N;
+  const size_t need = (size_t)rvo3d::orca_ws_slots(a->max_neighbors, a->max_buildings) * 6 * EN * sizeof(double);
+  if (need > h->orca_ws_bytes) {  // rvo3d_orca_vel's workspace, grown as it grows it
+    if (h->orca_ws) (void)hipFree(h->orca_ws);
+    h->orca_ws = nullptr;
+    h->orca_ws_bytes = 0;
+    HIP_TRY(hipMalloc((void**)&h->orca_ws, need));
+    h->orca_ws_bytes = need;
+  }
+  const rvo3d::ShieldArgs Y{a->time_horizon, a->time_step, a->max_speed, a->neighbor_dist * a->neighbor_dist, a->reach,
+                            a->below, a->clear_xy, a->max_neighbors, a->max_buildings, a->action, a->out_action,
+                            a->pref_vel, a->out_vel, a->status, a->flags, a->slack,
+                            reinterpret_cast<long long*>(a->totals), h->orca_ws, EN};
+  const int T = (int)align_up((size_t)h->P.N, 64);
+  hipLaunchKernelGGL(h->counted ? rvo3d::shield_counted_kernel : rvo3d::shield_kernel, dim3((unsigned)h->P.E),
+                     dim3((unsigned)T), rvo3d::shield_lds_bytes(T), static_cast<hipStream_t>(stream), h->P, Y,
+                     building_vel_args(m, dt));
+  HIP_TRY(hipGetLastError());
+  return RVO3D_OK;
+  RVO3D_API_END
+}
+
 int rvo3d_vel_command(rvo3d_env* h, const double* vel, double* action, uint8_t* clipped, void* stream) {
   RVO3D_API_BEGIN
   if (!h) return fail(RVO3D_ERR_INVALID, "null handle");

@@ -38,7 +38,8 @@
 // rvo3d_motion_kernels.hpp (moving buildings: the per-env records patrol, the per-cell lists are rebuilt in place),
 // rvo3d_rvo_city_kernels.hpp (the classical RVO selection with every candidate swept against the buildings),
 // rvo3d_orca_rules.hpp / rvo3d_orca_kernels.hpp (the ORCA velocity: one plane per neighbour and building, the four linear
-// programs; the converter from a velocity to the step's action), rvo3d_mfma_tiles.hpp (what the three
+// programs; the converter from a velocity to the step's action), rvo3d_shield_rules.hpp / rvo3d_shield_kernels.hpp (the
+// action shield: ORCA's planes and program on the velocity an action would fly), rvo3d_mfma_tiles.hpp (what the three
 // matrix-core policy kernels share: operand types, fragment maps, bf16 pack / split, the split product), rvo3d_policy_mlp.hpp (config 3's MLP(256, 256)
 // policy step on the matrix cores), rvo3d_policy_mlp_x3.hpp (the same step with split-bf16 products: float32-class), rvo3d_policy_rnn_tiles.hpp (the
 // biGRU actor-critic's step for rows with velocity-obstacle rows, in 32-row tiles on the matrix cores).
@@ -58,6 +59,7 @@
 #include "rvo3d_motion_kernels.hpp"
 #include "rvo3d_rvo_city_kernels.hpp"
 #include "rvo3d_orca_kernels.hpp"
+#include "rvo3d_shield_kernels.hpp"
 #include "rvo3d_mfma_tiles.hpp"
 #include "rvo3d_policy_mlp.hpp"
 #include "rvo3d_policy_mlp_x3.hpp"

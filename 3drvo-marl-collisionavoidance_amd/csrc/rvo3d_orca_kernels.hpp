@@ -43,6 +43,76 @@ __host__ __device__ inline int orca_ws_slots(int max_neighbors, int max_building
 }
 __host__ __device__ inline size_t orca_lds_bytes(int T) { return (size_t)T * 11 * sizeof(double); }
 
+// ---- what orca_body and shield_body (rvo3d_shield_kernels.hpp) share: the neighbour scan, the building gate and the
+// plane construction, on the env's drone records in LDS (x y z vx vy vz r, [T] each).  `work`: the lane wants planes.
+
+// Rule 2: the nearest neighbours among the env's N drones.
+__device__ __forceinline__ void orca_scan_neighbors(const double* lx, int T, int N, int d, bool work, const Drone& S,
+                                                    double nd2, OrcaSlots<kOrcaMaxNeighbors>& nbr) {
+  orca_slots_clear(nbr);
+  if (work) {
+    for (int j = 0; j < N; ++j) {
+      if (j == d) continue;
+      const double rx = lx[j] - S.x, ry = lx[T + j] - S.y, rz = lx[2 * T + j] - S.z;
+      const double d2 = (rx * rx + ry * ry) + rz * rz;
+      if (d2 < nd2) orca_slots_insert(nbr, d2, j);
+    }
+  }
+}
+
+// Rule 3: the nearest buildings that pass the gate, the env's nb records staged in tiles of T.  Every lane of the
+// workgroup calls it: it holds barriers (nb is the same for every env).
+__device__ __forceinline__ void orca_gate_buildings(const double* rec, int nb, int T, int d, bool work, const Drone& S,
+                                                    double reach, double below, double* s_bx, double* s_by, double* s_bh,
+                                                    double* s_br, OrcaSlots<kOrcaMaxBuildings>& bs) {
+  orca_slots_clear(bs);
+  for (int t0 = 0; t0 < nb; t0 += T) {
+    __syncthreads();  // the tile before this one has been read
+    if (t0 + d < nb) {
+      const double* b = rec + (size_t)(t0 + d) * 4;
+      s_bx[d] = b[0]; s_by[d] = b[1]; s_bh[d] = b[2]; s_br[d] = b[3];
+    }
+    __syncthreads();
+    if (!work) continue;
+    const int m = nb - t0 < T ? nb - t0 : T;
+    for (int j = 0; j < m; ++j) {
+      const BuildingPair q = building_pair(S.x, S.y, S.z, S.r, s_bx[j], s_by[j], s_bh[j], s_br[j], reach, below);
+      if (q.pass) orca_slots_insert(bs, q.gap, t0 + j);
+    }
+  }
+}
+
+// Rules 4 and 5: the planes, buildings first.  share(j): what the lane takes of the avoidance of neighbour j.
+template <class Share>
+__device__ __forceinline__ void orca_put_planes(const OrcaWsStore& planes, const double* lx, int T, int e, const Drone& S,
+                                                const OrcaSlots<kOrcaMaxNeighbors>& nbr, int kn,
+                                                const OrcaSlots<kOrcaMaxBuildings>& bs, int kb, const double* rec, int nb,
+                                                const BuildingVelArgs& V, double tau, double time_step, double clear_xy,
+                                                Share share) {
+  const OrcaV3 vi = orca_v3(S.vx, S.vy, S.vz);
+  int branch;
+#pragma unroll 1
+  for (int i = 0; i < kb; ++i) {
+    const int32_t idx = orca_slots_index(bs, i);  // (a kept index is a live record of env e: below nb, never a filler)
+    const double* b = rec + (size_t)idx * 4;
+    const double bx = b[0], by = b[1];
+    MotionVel vb{0.0, 0.0};
+    if (V.speed) {
+      const size_t m = (size_t)e * (size_t)nb + (size_t)idx;
+      vb = motion_velocity(bx, by, V.leg[m], V.ends + m * 4, V.speed[m], V.dt);
+    }
+    planes.put(i, orca_plane(orca_v3(bx - S.x, by - S.y, 0.0), orca_v3(S.vx - vb.x, S.vy - vb.y, 0.0),
+                             (S.r + b[3]) + clear_xy, tau, time_step, 1.0, vi, &branch));
+  }
+#pragma unroll 1
+  for (int i = 0; i < kn; ++i) {
+    const int32_t j = orca_slots_index(nbr, i);
+    planes.put(kb + i, orca_plane(orca_v3(lx[j] - S.x, lx[T + j] - S.y, lx[2 * T + j] - S.z),
+                                  orca_v3(S.vx - lx[3 * T + j], S.vy - lx[4 * T + j], S.vz - lx[5 * T + j]),
+                                  S.r + lx[6 * T + j], tau, time_step, share(j), vi, &branch));
+  }
+}
+
 // rvo_city_body's geometry: one workgroup per env, one lane per drone, T = align_up(N, 64) threads.  LDS: the env's drone
 // records (x y z vx vy vz r, 7 T doubles), which the neighbour scan and then the drone planes read, and behind them the
 // building records in tiles of T (x y h r, 4 T doubles) for the gate.  The sorted slots (16 neighbours, 8 buildings)
@@ -73,36 +143,14 @@ __device__ __forceinline__ void orca_body(const Params& P, const OrcaArgs& Y, co
 
   // ---- rule 2: the nearest neighbours ----
   OrcaSlots<kOrcaMaxNeighbors> nbr;
-  orca_slots_clear(nbr);
-  if (active) {
-    for (int j = 0; j < N; ++j) {
-      if (j == d) continue;
-      const double rx = lx[j] - S.x, ry = lx[T + j] - S.y, rz = lx[2 * T + j] - S.z;
-      const double d2 = (rx * rx + ry * ry) + rz * rz;
-      if (d2 < Y.nd2) orca_slots_insert(nbr, d2, j);
-    }
-  }
+  orca_scan_neighbors(lx, T, N, d, active, S, Y.nd2, nbr);
 
   // ---- rule 3: the nearest buildings that pass the gate ----
   const ColdC& C = P.cold();
-  const int nb = C.nb;  // the same for every env: the barriers below are uniform
+  const int nb = C.nb;  // the same for every env: the barriers of the gate are uniform
   const double* const rec = C.bld + (size_t)e * C.bld_stride;
   OrcaSlots<kOrcaMaxBuildings> bs;
-  orca_slots_clear(bs);
-  for (int t0 = 0; t0 < nb; t0 += T) {
-    __syncthreads();  // the tile before this one has been read
-    if (t0 + d < nb) {
-      const double* b = rec + (size_t)(t0 + d) * 4;
-      s_bx[d] = b[0]; s_by[d] = b[1]; s_bh[d] = b[2]; s_br[d] = b[3];
-    }
-    __syncthreads();
-    if (!active) continue;
-    const int m = nb - t0 < T ? nb - t0 : T;
-    for (int j = 0; j < m; ++j) {
-      const BuildingPair q = building_pair(S.x, S.y, S.z, S.r, s_bx[j], s_by[j], s_bh[j], s_br[j], Y.reach, Y.below);
-      if (q.pass) orca_slots_insert(bs, q.gap, t0 + j);
-    }
-  }
+  orca_gate_buildings(rec, nb, T, d, active, S, Y.reach, Y.below, s_bx, s_by, s_bh, s_br, bs);
   // (no barrier from here on)
 
   if (!active) {  // a ghost's row, or a lane past the env's rows
@@ -122,28 +170,8 @@ __device__ __forceinline__ void orca_body(const Params& P, const OrcaArgs& Y, co
   const int kn = nbr.seen < Y.max_neighbors ? nbr.seen : Y.max_neighbors;
   const OrcaWsStore planes{Y.ws + (size_t)g, Y.ws_ld};
   const OrcaWsStore proj{Y.ws + (size_t)g + (size_t)(Y.max_neighbors + Y.max_buildings) * 6 * Y.ws_ld, Y.ws_ld};
-  const OrcaV3 vi = orca_v3(S.vx, S.vy, S.vz);
-  int branch;
-#pragma unroll 1
-  for (int i = 0; i < kb; ++i) {
-    const int32_t idx = orca_slots_index(bs, i);  // (a kept index is a live record of env e: below nb, never a filler)
-    const double* b = rec + (size_t)idx * 4;
-    const double bx = b[0], by = b[1];
-    MotionVel vb{0.0, 0.0};
-    if (V.speed) {
-      const size_t m = (size_t)e * (size_t)nb + (size_t)idx;
-      vb = motion_velocity(bx, by, V.leg[m], V.ends + m * 4, V.speed[m], V.dt);
-    }
-    planes.put(i, orca_plane(orca_v3(bx - S.x, by - S.y, 0.0), orca_v3(S.vx - vb.x, S.vy - vb.y, 0.0),
-                             (S.r + b[3]) + Y.clear_xy, Y.tau, Y.time_step, 1.0, vi, &branch));
-  }
-#pragma unroll 1
-  for (int i = 0; i < kn; ++i) {
-    const int32_t j = orca_slots_index(nbr, i);
-    planes.put(kb + i, orca_plane(orca_v3(lx[j] - S.x, lx[T + j] - S.y, lx[2 * T + j] - S.z),
-                                  orca_v3(S.vx - lx[3 * T + j], S.vy - lx[4 * T + j], S.vz - lx[5 * T + j]),
-                                  S.r + lx[6 * T + j], Y.tau, Y.time_step, 0.5, vi, &branch));
-  }
+  orca_put_planes(planes, lx, T, e, S, nbr, kn, bs, kb, rec, nb, V, Y.tau, Y.time_step, Y.clear_xy,
+                  [](int) { return 0.5; });  // every drone takes half
 
   // ---- rules 1 and 6 ----
   double cur[3], des[3];

@@ -139,6 +139,14 @@ class OrcaArgs(C.Structure):
                [(n, C.c_void_p) for n in ("n_neighbors", "n_buildings", "status", "slack")]
 
 
+class ShieldArgs(C.Structure):
+    """rvo3d_shield_args (rvo3d_shield_action)."""
+    _fields_ = [("time_horizon", C.c_double), ("time_step", C.c_double), ("max_speed", C.c_double),
+                ("neighbor_dist", C.c_double), ("max_neighbors", C.c_int32), ("max_buildings", C.c_int32),
+                ("reach", C.c_double), ("below", C.c_double), ("clear_xy", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("action", "out_action", "pref_vel", "out_vel", "status", "flags", "slack", "totals")]
+
+
 class StateView(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("px", "py", "pz", "vx", "vy", "vz", "yaw", "pitch", "real_len", "max_dev",
@@ -161,6 +169,7 @@ SYMBOLS = ("rvo3d_create", "rvo3d_destroy", "rvo3d_load_world", "rvo3d_set_env_b
            "rvo3d_building_rows_moving",
            "rvo3d_observe_envs", "rvo3d_set_reward_f64",
            "rvo3d_des_vel", "rvo3d_rvo_vel", "rvo3d_rvo_vel_city", "rvo3d_orca_vel", "rvo3d_vel_command",
+           "rvo3d_shield_action",
            "rvo3d_state_ptrs", "rvo3d_get_state", "rvo3d_set_state",
            "rvo3d_error_flags", "rvo3d_launch_info", "rvo3d_kernel_name", "rvo3d_version", "rvo3d_last_error")
 
@@ -242,6 +251,7 @@ def lib():
     L.rvo3d_rvo_vel_city.argtypes = [vp, C.POINTER(RvoCityArgs), C.POINTER(BuildingMotionArgs), C.c_double, vp]
     L.rvo3d_orca_vel.argtypes = [vp, C.POINTER(OrcaArgs), C.POINTER(BuildingMotionArgs), C.c_double, vp]
     L.rvo3d_vel_command.argtypes = [vp] * 5
+    L.rvo3d_shield_action.argtypes = [vp, C.POINTER(ShieldArgs), C.POINTER(BuildingMotionArgs), C.c_double, vp]
     L.rvo3d_state_ptrs.argtypes = [vp, C.POINTER(StateView)]
     L.rvo3d_get_state.argtypes = [vp] * 12
     L.rvo3d_set_state.argtypes = [vp] * 12

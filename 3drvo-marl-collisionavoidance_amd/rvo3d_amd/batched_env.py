@@ -536,6 +536,43 @@ class BatchedDroneEnv:
                                                 self._stream()), "rvo3d_vel_command")
         return (out, clipped) if return_clipped else out
 
+    def shield_action(self, action, time_horizon: float = 5.0, time_step: float = 1.0, max_speed: float = 2.0,
+                      neighbor_dist: float = 10.0, max_neighbors: int = 10, max_buildings: int = 4, reach: float = 10.0,
+                      below: float = 1.0, clear_xy: float = 0.0, diagnostics: bool = False, totals=None):
+        """The action shield (rvo3d_shield_action; the rules are in include/rvo3d.h): ORCA as a safety filter behind any
+        controller.  For every drone the velocity the next step() would fly for `action` [E, N, 3] is held against the
+        ORCA planes of the current state (orca_vel's, except that a parked neighbour takes no share); where it satisfies
+        them the action comes back bit for bit, where it does not it is replaced by the velocity_command for the
+        permitted velocity nearest to it.  Parked drones, rows with a non-finite action and ghost rows are not judged.
+        Returns [E, N, 3] float64; with diagnostics=True also a dict of pref_vel, out_vel ([E, N, 3] float64), status
+        (int32, orca_vel's; 0 not judged), flags (uint8: 8 intervened, 1 / 2 / 4 the command's clipped components) and
+        slack (float64), [E, N] each.  totals: an int64 [E, 4] device tensor the call adds the env's judged, intervened,
+        fallback (status 3) and clipped-command rows to; the caller zeroes it.  The motion attached now is picked up at
+        every call.  One launch, no synchronisation.
+        Limits: a command that clips does not reach the permitted velocity; on a handle with action_decimals >= 0 the
+        step quantises the action and the shield predicts the unquantised one; buildings are cylinders of unlimited
+        height; the half share assumes that the other drone is shielded too."""
+        a_in = torch.as_tensor(action, device=self.device).to(torch.float64).contiguous()
+        if tuple(a_in.shape) != (self.E, self.N, 3):
+            raise ValueError(f"action must be [{self.E}, {self.N}, 3], not {tuple(a_in.shape)}")
+        if totals is not None and (totals.dtype != torch.int64 or tuple(totals.shape) != (self.E, 4)
+                                   or not totals.is_contiguous() or totals.device != a_in.device):
+            raise ValueError(f"totals must be a contiguous int64 [{self.E}, 4] tensor on the env's device")
+        out = torch.empty((self.E, self.N, 3), dtype=torch.float64, device=self.device)
+        diag = {}
+        names = ("pref_vel", "out_vel", "status", "flags", "slack")
+        if diagnostics:
+            for name, dt_ in zip(names, (torch.float64, torch.float64, torch.int32, torch.uint8, torch.float64)):
+                diag[name] = torch.empty((self.E, self.N, 3) if name.endswith("_vel") else (self.E, self.N), dtype=dt_,
+                                         device=self.device)
+        a = _lib.ShieldArgs(float(time_horizon), float(time_step), float(max_speed), float(neighbor_dist),
+                            int(max_neighbors), int(max_buildings), float(reach), float(below), float(clear_xy),
+                            a_in.data_ptr(), out.data_ptr(), *[diag[n].data_ptr() if diagnostics else None for n in names],
+                            None if totals is None else totals.data_ptr())
+        m, dt = self._motion_args()
+        _lib.check(_lib.lib().rvo3d_shield_action(self._h, C.byref(a), m, dt, self._stream()), "rvo3d_shield_action")
+        return (out, diag) if diagnostics else out
+
     # -- state ------------------------------------------------------------------------
     def get_state(self):
         E, N, dev = self.E, self.N, self.device

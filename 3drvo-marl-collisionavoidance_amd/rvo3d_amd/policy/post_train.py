@@ -40,6 +40,18 @@ near_margin of touching), from rvo3d_safety_scan on the state behind every step 
 loop calls rvo3d_eval_account_safety in place of rvo3d_eval_account, which folds them into four more record arrays on
 the device; the host loop calls env.safety() and folds by the same rules.  `policy_test` returns what it returns
 without it and leaves the summary (rvo3d_amd.safety.summarize_safety) in self.safety.
+
+shield=dict(...) (opt-in, either loop, every policy_type) puts the action shield behind the controller: the action that
+would go to env.step - eval_action's output for "drl", _action()'s otherwise - goes through env.shield_action(**shield)
+first (rvo3d_shield_action, include/rvo3d.h: the action comes back untouched where the velocity it would fly satisfies
+the ORCA planes of the current state, and as the command for the nearest permitted velocity where it does not).  One more
+launch per step and no host synchronisation: the evaluator owns one [E, 4] int64 tensor of totals on the device for the
+whole policy_test, which every call adds to, and reads it once at the end into self.shield: `judged` (drone-steps the
+shield judged) and `intervened_share`, `fallback_share` (no permitted velocity: ORCA's fallback) and `clipped_share`
+(intervened with a command that clipped), each over `judged`.  The totals are over ALL steps flown: the episodes beyond
+an env's quota, which the records do not count, and with fused=True the at most poll_every - 1 steps behind the last
+record are included.  Shielding inside the trainer's rollouts is out of scope: the stored action, its log-probability
+and the flown action would diverge.
 """
 from __future__ import annotations
 
@@ -91,7 +103,7 @@ def summarize_records(step, env, length, ret, speed, flags, policy_name="policy"
 class post_train:
     def __init__(self, env, num_episodes=100, max_ep_len=150, acceler_vel=1.0, render=False,
                  save=False, neighbor_region=4, neighbor_num=5, args=None, fused=False, policy_kernel=None,
-                 poll_every=8, seed=0, safety=False, near_margin=0.5, rvo=None, command="raw", **kwargs):
+                 poll_every=8, seed=0, safety=False, near_margin=0.5, rvo=None, command="raw", shield=None, **kwargs):
         """fused: the device-side loop (module docstring); policy_kernel: None (policy.step_tensors) or the
         KernelPolicyStep kind that runs the policy - "mlp", "mlp_x3" (the MLP actor-critic, bf16 / float32-class),
         "rnn_tiles" or "rnn_tiles_x3" (the biGRU actor-critic, likewise) - either loop; poll_every: steps between two host
@@ -100,7 +112,8 @@ class post_train:
         classical controller policy_test flies for policy_type "rvo" (env.rvo_vel), "rvo_city" (env.rvo_vel_city) and
         "orca" (env.orca_vel); command: what becomes of the controller's velocity (policy types without a network) - "raw":
         handed to env.step as it is, which reads it as acceleration, yaw and pitch increments (the reference's glue);
-        "velocity": through env.velocity_command first, so that the step flies that velocity."""
+        "velocity": through env.velocity_command first, so that the step flies that velocity; shield: None, or the keyword
+        arguments of env.shield_action that every action goes through before the step (module docstring)."""
         if command not in ("raw", "velocity"):
             raise ValueError(f"command must be 'raw' or 'velocity', not {command!r}")
         self.command = command
@@ -117,6 +130,10 @@ class post_train:
         self.rvo = dict(rvo or {})
         if "diagnostics" in self.rvo:
             raise ValueError("rvo= carries the controller's parameters, not diagnostics")
+        self.shield_args = None if shield is None else dict(shield)
+        if self.shield_args is not None and {"diagnostics", "totals"} & set(self.shield_args):
+            raise ValueError("shield= carries the shield's parameters, not diagnostics or totals")
+        self.shield = None   # the shield's shares once policy_test ran with shield=dict(...)
         self.env = env
         self.num_episodes = num_episodes
         self.max_ep_len = max_ep_len
@@ -189,12 +206,29 @@ class post_train:
         v = self._fly()
         return self.env.velocity_command(v) if self.command == "velocity" else v
 
+    def _shielded(self, action):
+        """The action env.step gets: through env.shield_action with shield=dict(...), else as it is."""
+        if self.shield_args is None:
+            return action
+        return self.env.shield_action(action, totals=self._shield_totals, **self.shield_args)
+
+    def _shield_summary(self):
+        """self.shield from the totals on the device: the one host read of the shield (module docstring)."""
+        if self.shield_args is None:
+            return
+        judged, intervened, fallback, clipped = (int(x) for x in self._shield_totals.sum(dim=0).cpu())
+        share = lambda n: n / judged if judged else 0.0
+        self.shield = dict(judged=judged, intervened_share=share(intervened), fallback_share=share(fallback),
+                           clipped_share=share(clipped))
+
     def policy_test(self, policy_type="drl", policy_path=None, policy_name="policy", result_path=None,
                     result_name="/result.txt", policy=None, policy_dict=False, **_unused):
         env = self.env
         E, N, dev = env.E, env.N, env.device
         act_fn = None
         self._fly = self._classical(policy_type)
+        if self.shield_args is not None:
+            self._shield_totals = torch.zeros((E, 4), dtype=torch.int64, device=dev)
         if policy_type == "drl":
             act_fn = self.load_policy(policy if policy is not None else policy_path,
                                       self.std_factor, policy_dict=policy_dict)
@@ -230,6 +264,7 @@ class post_train:
                 action = (torch.as_tensor(self.acceler_vel, dtype=torch.float32, device=dev) * a_inc).double() + vel
             else:
                 action = self._action()
+            action = self._shielded(action)
             obs, cnt, rew, done, info, fin = env.step(action)             # plain drone_step
             if ghost is None:
                 speed_sum += torch.linalg.vector_norm(env.vel, dim=-1).mean(dim=1)
@@ -282,6 +317,7 @@ class post_train:
                 speed_sum = torch.where(ended, torch.zeros_like(speed_sum), speed_sum)
                 if self.with_safety:
                     run = [torch.where(ended, inf, r) for r in run[:3]] + [torch.where(ended, torch.zeros_like(run[3]), run[3])]
+        self._shield_summary()
         length, ret, speed, flags = zip(*records)
         if self.with_safety:
             ms, mb, mw, nr, dr = (np.asarray(x) for x in zip(*safety_records))
@@ -329,6 +365,7 @@ class post_train:
                 action = env.eval_action(a, self.acceler_vel)
             else:
                 action = self._action()
+            action = self._shielded(action)
             obs, cnt, rew, done, info, fin = env.step(action)             # plain drone_step
             if self.with_safety:
                 _lib.check(L.rvo3d_eval_account_safety(env._h, p(rew), p(done), p(info), p(fin), self.max_ep_len, quota,
@@ -349,6 +386,7 @@ class post_train:
                         raise ValueError("observation contains NaN/Inf")
                 if int(t["remaining"].item()) <= 0:
                     break
+        self._shield_summary()
         e_idx = np.repeat(np.arange(E), quota)   # env of record [e][k]; remaining <= 0: every slot is filled
         # the records as the device left them, [E][quota] each (kept for the caller: self.records)
         rec = self.records = {k: t[k].cpu().numpy() for k in rec_keys}

@@ -921,6 +921,60 @@ int rvo3d_orca_vel(rvo3d_env *h, const rvo3d_orca_args *args,
  * RVO3D_ERR_STATE without a loaded world, RVO3D_ERR_INVALID for a null vel / action. */
 int rvo3d_vel_command(rvo3d_env *h, const double *vel, double *action, uint8_t *clipped, void *stream);
 
+/* The action shield: ORCA as a safety filter behind any controller.  For every drone it takes the velocity the next
+ * rvo3d_step would give the drone for `action`, and hands the action back untouched where that velocity satisfies
+ * every ORCA plane of the current state; where it does not, the action is replaced by the command (rvo3d_vel_command)
+ * for the permitted velocity nearest to it.  motion, dt: as for rvo3d_orca_vel.  Per live drone i of env e:
+ *   S1. Preferred velocity: the velocity behind the step for this action, drone.kinematicstep in the step's own
+ *       arithmetic (csrc/rvo3d_shield_rules.hpp: shield_pref is the statement):
+ *         speed = max(0, |v| + clamp(a0, -1, 1)),  |v| = sqrt(fma(v_z, v_z, fma(v_y, v_y, v_x * v_x))),
+ *         yaw' = np_mod(yaw + clamp(90 a1, -90, 90), 360),  pitch' = clamp(pitch + clamp(90 a2, -90, 90), -90, 90),
+ *         (s_y, c_y) = sincos(yaw' * 0.017453292519943295), (s_p, c_p) likewise of pitch',
+ *         pref = ((speed * c_p) * c_y, (speed * c_p) * s_y, speed * s_p).
+ *       On a handle with action_decimals >= 0 the step quantises the action first; S1 predicts the unquantised one
+ *       (evaluation handles use -1).
+ *   S2. Planes: rules 2-5 of rvo3d_orca_vel on the current state, with one change: a neighbour whose dest flag is set
+ *       takes no share - the step parks it whatever anyone commands - so the share against it is 1, not 0.5.
+ *   S3. Program: rule 6 of rvo3d_orca_vel for the point of the ball |v| <= max_speed nearest pref: v, status, slack.
+ *   S4. Identity where safe.  The row is intervened iff v != pref in some component.  Not intervened: the three doubles
+ *       of out_action are the three doubles of action, bit for bit.  Intervened: out_action is rvo3d_vel_command's
+ *       action for w = v on the drone's state.  flags: 8 for an intervened row, plus the command's clipped bits
+ *       (1, 2, 4: component k was clipped, the step then does not reach v).  out_vel = v for every judged row.
+ *   S5. Not judged - the action passes through, status, flags and slack are 0, pref_vel and out_vel are 0, the row
+ *       enters no total: a drone whose dest flag is set (it still stands in the others' neighbour scans with the state
+ *       on file); a row whose action has a non-finite component; a ghost row of a counted handle (its out_action is
+ *       0, as rvo3d_vel_command writes ghosts; its state is not read).
+ *   S6. totals (nullable, DEVICE [E][4] int64): the call ADDS to totals[e] the number of env e's rows that were judged,
+ *       intervened, of status 3 (the fallback), and intervened with a clipped command.  The caller zeroes the array.
+ * S2 and S3 are float64, rounded operation by operation, and defined to the last bit as rvo3d_orca_vel is, given pref.
+ * S1 and the command go through the device library's sincos / atan2 / asin: against a host evaluation they agree to a
+ * tolerance, not to the bit; against the step of the same device S1 is the same calls on the same inputs.
+ * Limits.  A command that clips does not reach v.  Buildings are upright cylinders of unlimited height, as in
+ * rvo3d_orca_vel.  The half share assumes that the other drone is shielded too.
+ * One launch, no synchronisation and no atomics (one workgroup owns its env); the planes live in the workspace
+ * rvo3d_orca_vel uses, allocated by the first call of either and grown by a call that needs more.  Calls on one handle
+ * must not overlap on different streams.  Every argument check runs before the first HIP call and a refused call writes
+ * nothing: the codes of rvo3d_orca_vel, RVO3D_ERR_INVALID also for a null action / out_action. */
+typedef struct rvo3d_shield_args {
+  double time_horizon;                     /* finite > 0: tau                                              */
+  double time_step;                        /* finite > 0                                                   */
+  double max_speed;                        /* finite >= 0                                                  */
+  double neighbor_dist;                    /* finite > 0                                                   */
+  int32_t max_neighbors, max_buildings;    /* 1..16, 0..8                                                  */
+  double reach, below;                     /* building gate, finite > 0 / finite >= 0                      */
+  double clear_xy;                         /* finite >= 0                                                  */
+  const double *action;                    /* DEVICE [E][N][3], required                                   */
+  double *out_action;                      /* DEVICE [E][N][3], required; may be action itself             */
+  /* diagnostics, DEVICE, each nullable: [E][N][3] f64, [E][N][3] f64, [E][N] i32, [E][N] u8, [E][N] f64 */
+  double *pref_vel, *out_vel;
+  int32_t *status;
+  uint8_t *flags;
+  double *slack;
+  int64_t *totals;                         /* DEVICE [E][4], nullable: judged, intervened, status 3, clipped */
+} rvo3d_shield_args;
+int rvo3d_shield_action(rvo3d_env *h, const rvo3d_shield_args *args,
+                        const rvo3d_building_motion *motion, double dt, void *stream);
+
 /* Zero-copy views of the state arrays, READ-ONLY: the step keeps values derived from the
  * state on file between calls (des_vel, the in-range words of the pair gate, the current /
  * previous waypoint); state is changed through rvo3d_set_state / rvo3d_reset*, which bring
